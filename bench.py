@@ -26,6 +26,14 @@ Workloads (`--workload`, default C3 on 1 GPU, C4 on N):
       input; --no-mismatches is a no-op in the reference, bwt.py:3105)
 The output sha256 is checked against the reference-pipeline golden
 (tests/golden/expected_large.json) when the workload has one.
+
+A plain run sets up, warms up, times the steps and prints the line; every
+figure in it comes from those steps.  `--full` adds the legs that take runs of
+their own (cpu_baseline, fm_all_motifs_1_10, cli_drop_in; `--no-cpu-baseline`,
+`--no-fm`, `--no-cli` drop single ones); without it these fields are null.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/*.npy
+(dump_outputs below); the inputs are seeded, so two builds run with the same
+arguments can be compared array for array.
 """
 import argparse
 import hashlib
@@ -224,6 +232,51 @@ def word_compares(n: int, U: int, mc: int = 3, lmin: int = 1):
     return dict(dense=dense, sparse=sparse, dense_equivalent=every)
 
 
+# --dump-outputs: bytes each array may take on disk (61 MB in all, under the 64 MB a dump may hold)
+DUMP_BUDGET = dict(records_int=30_000_000, records_float=17_000_000, repeat_tab_bytes=14_000_000)
+DUMP_SEED = 20240607
+
+
+def sample_rows(arr, max_bytes: int, seed: int = DUMP_SEED):
+    """arr itself when it fits in max_bytes, else a fixed sample of its rows
+    (ascending indices drawn without replacement by a generator seeded with
+    `seed`: the same rows for the same row count in every run)."""
+    import numpy as np
+    row = max(1, arr.nbytes // max(1, len(arr)))
+    keep = max_bytes // row
+    if len(arr) <= keep:
+        return arr
+    idx = np.sort(np.random.default_rng(seed).choice(len(arr), size=keep, replace=False))
+    return arr[idx]
+
+
+def dump_outputs(dirname: str, job, data: bytes):
+    """What a caller of the timed path holds after the last timed step, as
+    float arrays under dirname (this rank's records; the whole file):
+      records_int.npy       float64 [n, 9]  bwtmi_job_get_records' integer columns (start, end, length,
+                            tier, n_copies_eval, max_mm, score, flags, chrom_id), exact in float64
+      records_float.npy     float64 [n, 5]  its doubles (copies, mismatch_rate, confidence,
+                            percent_matches, percent_indels)
+      repeat_tab_bytes.npy  float32 [m]     the bytes of the written repeat.tab (motifs and number
+                            formats included)
+    each cut to its DUMP_BUDGET by sample_rows when larger.  Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    recs = job.records()
+    n = len(recs)
+    arrays = dict(records_int=recs._ints[:n].astype(np.float64),
+                  records_float=recs._dbls[:n].astype(np.float64),
+                  repeat_tab_bytes=np.frombuffer(data, dtype=np.uint8))
+    shapes = {}
+    for name, arr in arrays.items():
+        itemsize = 4 if name == "repeat_tab_bytes" else 8
+        arr = sample_rows(arr, DUMP_BUDGET[name] * arr.dtype.itemsize // itemsize)
+        arr = np.ascontiguousarray(arr, dtype=np.float32 if itemsize == 4 else np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        shapes[name] = list(arr.shape)
+    return shapes
+
+
 def launch_ranks(n: int, argv, script: str = None) -> int:
     """`bench.py --gpus N` without an external launcher: N rank processes of
     this script, one per GPU (bwtmi.dist.launch_ranks: RANK / LOCAL_RANK /
@@ -240,11 +293,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=["auto"] + sorted(WORKLOADS), default="auto")
     ap.add_argument("--contig-bp", type=int, default=0, help="override every contig length (tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that need runs of their own: the CPU baseline, "
+                         "the all-motif FM search and the in-process drop-in CLI (default: these fields are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's records and repeat.tab bytes as DIR/*.npy (rank 0)")
     ap.add_argument("--cpu-sample-bp", type=int, default=30_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-index", action="store_true", help="skip the FM index (scan-only step)")
-    ap.add_argument("--no-fm", action="store_true", help="skip the all-motif FM search report")
-    ap.add_argument("--no-cli", action="store_true", help="skip the in-process drop-in CLI timing")
+    ap.add_argument("--no-fm", action="store_true", help="with --full: skip the all-motif FM search report")
+    ap.add_argument("--no-cli", action="store_true", help="with --full: skip the in-process drop-in CLI timing")
     ap.add_argument("--stages", action="store_true", help="print per-stage times to stderr")
     ap.add_argument("--host-load", action="store_true",
                     help="whole-file load on the host + upload (default: built on the device from the file image)")
@@ -255,6 +313,8 @@ def main():
     ap.add_argument("--pmc-summary", default=None,
                     help="tools/pmc_traffic.py output giving HBM bytes per launch (roofline.traffic)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         return launch_ranks(a.gpus, sys.argv[1:])
@@ -398,6 +458,7 @@ def main():
     with open(out, "rb") as f:
         data = f.read()
     rows, digest = data.count(b"\n") - 1, hashlib.sha256(data).hexdigest()
+    dumped = dump_outputs(a.dump_outputs, job, data) if a.dump_outputs else None
     golden = None
     gpath = os.path.join(REPO, "tests", "golden", "expected_large.json")
     if not a.contig_bp and os.path.exists(gpath):
@@ -471,14 +532,16 @@ def main():
                                                meaning="every word for every unit length: the work the sampling "
                                                        "avoids, not work done"))
     e2e_gbs = B_ALG_PER_BASE * total_bp / (elapsed / a.steps) / 1e9
-    cpu = None if a.no_cpu_baseline else cpu_baseline(a.cpu_sample_bp, wl["sub_rate"], host["threads_per_rank"],
-                                                        wl.get("gaps"))
+    # the legs with runs of their own: only with --full
+    cpu = None
+    if a.full and not a.no_cpu_baseline:
+        cpu = cpu_baseline(a.cpu_sample_bp, wl["sub_rate"], host["threads_per_rank"], wl.get("gaps"))
     fm = None
-    if not a.no_fm:
+    if a.full and not a.no_fm:
         first = min(i for i in range(job.contig_count()) if job.contig_info(i)[1] > 0)
         fm = fm_all_motifs(job.contig_seq(first))
     cli = None
-    if world == 1 and not shared and not a.no_cli:
+    if a.full and world == 1 and not shared and not a.no_cli:
         cli = cli_drop_in(fa, ["--progress", "--jobs", "0"])
         cli["vs_step"] = round(min(cli["wall_s"]) * 1e3 / ms_step, 2)
         cli["golden_match"] = golden["sha256"] == cli["output_sha256"] if golden else None
@@ -528,6 +591,8 @@ def main():
         "value_resident_text": round(total_bp / 1e6 / ((ms_step - load_up) / 1e3), 3) if ms_step > load_up else None,
         "fm_all_motifs_1_10": fm,
         "cli_drop_in": cli,
+        "full": a.full,
+        "dumped_outputs": dumped,
     }
     print(json.dumps(line))
     if c is not None:
