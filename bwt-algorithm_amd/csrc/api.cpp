@@ -1,4 +1,5 @@
-// api.cpp -- the extern "C" boundary of libbwtmi.so (include/bwtmi.h).
+// api.cpp -- the extern "C" boundary of libbwtmi.so (include/bwtmi.h): the
+// entry points, the job's and the context's device bookkeeping, the lane runner.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -8,12 +9,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cctype>
-#include <condition_variable>
 #include <cstring>
 #include <exception>
-#include <fcntl.h>
-#include <sys/uio.h>
-#include <unistd.h>
 
 #include <memory>
 #include <mutex>
@@ -25,6 +22,7 @@
 
 #include "common.h"
 #include "device.h"
+#include "outfile.h"
 
 namespace bwtmi {
 
@@ -107,6 +105,15 @@ struct JobDev {
     int device = -1;
     std::vector<DevContig> seqs;
     Ctx *bg_ctx = nullptr;   // context whose background work reads these buffers (cleared by its join)
+    // the copies now belong on `dev`: another device's are dropped, one entry per contig
+    void rebind(int dev, size_t ncontigs) {
+        if (device >= 0 && device != dev) {
+            for (auto &s : seqs) s.buf.release();
+            seqs.clear();
+        }
+        device = dev;
+        seqs.resize(ncontigs);
+    }
 };
 
 // every entry point that touches a context: join its background work, select the device
@@ -116,185 +123,21 @@ static Ctx &use(Ctx &c) {
     return c;
 }
 
-// Output file descriptor: closed on every path; when the write fails part-way
-// (an exception or a short write) the file is cut to 0 bytes rather than left
-// holding a mix of old and new rows.
-struct OutFd {
-    int fd = -1;
-    bool ok = false;
-    explicit OutFd(const char *path) : fd(::open(path, O_WRONLY | O_CREAT, 0644)) {
-        if (fd < 0) fail(BWTMI_E_IO, "cannot open %s for writing", path);
-    }
-    ~OutFd() {
-        if (fd < 0) return;
-        if (!ok) (void)::ftruncate(fd, 0);
-        (void)::close(fd);
-    }
-    // cut to `size` (when whole) and close; false on error
-    bool finish(bool whole, size_t size) {
-        bool good = !whole || ::ftruncate(fd, (off_t)size) == 0;
-        ok = good;
-        good = (::close(fd) == 0) && good;
-        fd = -1;
-        return good;
-    }
-};
-
-// Buffers [p[k], p[k] + n[k]) written back to back at byte offset `at` of fd,
-// IOV_MAX at a time: one writer with large pwritev calls.  Buffered writes to
-// one file serialise on its inode lock, so parallel writers only contend: on
-// the box host a 55 MB file took 2.8-3.1 ms as one pwrite and 4.3-4.8 ms from
-// 16 threads (tools/write_bench.cpp, profiles/r06/write_bench_r06g.txt).
-// False on a short write.
-static bool pwrite_run(int fd, const char *const *p, const size_t *n, size_t cnt, size_t at) {
-    constexpr size_t kIov = 1024;
-    iovec v[kIov];
-    size_t k = 0, skip = 0;   // next buffer, bytes of it already written
-    while (k < cnt) {
-        size_t m = 0;
-        for (size_t j = k; j < cnt && m < kIov; ++j) {
-            const size_t off = j == k ? skip : 0;
-            if (n[j] <= off) continue;
-            v[m].iov_base = const_cast<char *>(p[j] + off);
-            v[m].iov_len = n[j] - off;
-            ++m;
-        }
-        if (m == 0) break;
-        const ssize_t w = ::pwritev(fd, v, (int)m, (off_t)at);
-        if (w <= 0) return false;
-        at += (size_t)w;
-        size_t left = (size_t)w;   // advance (k, skip) past the bytes written
-        while (k < cnt && left >= n[k] - skip) {
-            left -= n[k] - skip;
-            skip = 0;
-            ++k;
-        }
-        skip += left;
-    }
-    return true;
+// the stream and the two timing events of a new context (the device is current)
+static void ctx_create_streams(Ctx &c) {
+    HIPCHECK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    HIPCHECK(hipEventCreate(&c.ev0));
+    HIPCHECK(hipEventCreate(&c.ev1));
 }
 
-// parts[k] lands at byte offset at[k] of `path` (one writer, consecutive parts
-// in one pwritev).  `whole`: the parts are the whole file -- it is overwritten
-// in place and cut to at.back() bytes afterwards (the content is that of
-// open(path, 'w') + write; rewriting a file of the same size reuses its
-// page-cache pages).
-static void pwrite_parts(const char *path, bool whole, const std::vector<Text> &parts,
-                         const std::vector<size_t> &at, int threads) {
-    (void)threads;
-    OutFd out(path);
-    const int fd = out.fd;
-    std::vector<const char *> p;
-    std::vector<size_t> n;
-    bool good = true;
-    for (size_t k = 0; k < parts.size() && good;) {   // runs of parts that are consecutive in the file
-        size_t j = k, end = at[k];
-        p.clear();
-        n.clear();
-        while (j < parts.size() && at[j] == end) {
-            p.push_back(parts[j].data());
-            n.push_back(parts[j].size());
-            end += parts[j].size();
-            ++j;
-        }
-        good = pwrite_run(fd, p.data(), n.data(), p.size(), at[k]);
-        k = j;
-    }
-    if (!good) fail(BWTMI_E_IO, "short write to %s", path);   // ~OutFd cuts a whole-file write
-    if (!out.finish(whole, at.back())) fail(BWTMI_E_IO, "short write to %s", path);
+// v's elements in a malloc block for the caller (bwtmi_free); never null
+template <class T, class A>
+static T *malloc_copy(const std::vector<T, A> &v) {
+    auto *out = (T *)std::malloc(std::max<size_t>(1, v.size()) * sizeof(T));
+    if (!out) fail(BWTMI_E_NOMEM, "malloc");
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(T));
+    return out;
 }
-
-// One output file written by its own writer thread while the rows are being
-// formatted (bwtmi_job_write, bwtmi_job_write_async).  The formatting tasks
-// mark their part done; the writer pwritev's every run of consecutive done
-// parts in file order, the header first -- ONE writer, since buffered writes
-// to one file serialise on its inode lock (pwrite_run).  The content is that
-// of one open(path, 'w') + write: the file is overwritten in place and cut to
-// its size at the end (a short write or an error cuts it to 0).
-struct FileWrite {
-    OutFd out;
-    std::string path;
-    Rendered R;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<uint8_t> done;
-    size_t next = 0, off = 0;
-    bool started = false, rendered = false, aborted = false, header_done = false, bad = false;
-    std::thread th;
-    explicit FileWrite(const char *p) : out(p), path(p) {}
-    ~FileWrite() {
-        if (th.joinable()) {
-            abort();
-            th.join();
-        }
-    }
-    void part_done(size_t k) {   // (render_rows sized R.parts before the first part)
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (!started) {
-                done.assign(R.parts.size(), 0);
-                started = true;
-            }
-            done[k] = 1;
-        }
-        cv.notify_one();
-    }
-    void render_done() {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            rendered = true;
-        }
-        cv.notify_one();
-    }
-    void abort() {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            rendered = aborted = true;
-        }
-        cv.notify_one();
-    }
-    void run() {
-        std::unique_lock<std::mutex> lk(mu);
-        std::vector<const char *> wp;
-        std::vector<size_t> wn;
-        auto ready = [&] { return started && next < done.size() && done[next]; };
-        for (;;) {
-            cv.wait(lk, [&] { return aborted || rendered || (started && !header_done) || ready(); });
-            if (aborted) return;
-            if (!header_done) {   // the header exists once a part or the whole render is done
-                header_done = true;
-                const char *hp = R.header.data();
-                const size_t hn = R.header.size();
-                off = hn;
-                lk.unlock();
-                if (!pwrite_run(out.fd, &hp, &hn, 1, 0)) bad = true;
-                lk.lock();
-                continue;
-            }
-            if (ready()) {
-                const size_t at = off;
-                wp.clear();
-                wn.clear();
-                while (ready()) {
-                    wp.push_back(R.parts[next].data());
-                    wn.push_back(R.parts[next].size());
-                    off += R.parts[next].size();
-                    ++next;
-                }
-                lk.unlock();
-                if (!pwrite_run(out.fd, wp.data(), wn.data(), wp.size(), at)) bad = true;
-                lk.lock();
-                continue;
-            }
-            if (rendered) return;   // every part is done and written
-        }
-    }
-    // wait for the writer, cut the file to its size and close it; false on a short write
-    bool finish() {
-        if (th.joinable()) th.join();
-        return !bad && !aborted && out.finish(true, off);
-    }
-};
 
 }  // namespace bwtmi
 
@@ -316,6 +159,12 @@ struct bwtmi_job {
 };
 
 namespace {
+// an entry point that touches a job's device buffers through context c: the
+// other context whose background work still reads them is joined too
+Ctx &job_use(Ctx &c, bwtmi_job *job) {
+    if (job->dev.bg_ctx && job->dev.bg_ctx != &c) ctx_wait(*job->dev.bg_ctx);
+    return use(c);
+}
 // the job's file write in flight, if any: wait for it and report its error
 void write_join(bwtmi_job *job) {
     if (job->units_wr.joinable()) job->units_wr.join();
@@ -428,9 +277,7 @@ int bwtmi_open(int device, bwtmi_ctx **out) {
         // 1949 vs 1895 Mbp/s over 3 runs each); the scan's short waits poll
         // (scan_wait)
         if (hipSetDeviceFlags(hipDeviceScheduleBlockingSync) != hipSuccess) (void)hipGetLastError();
-        HIPCHECK(hipStreamCreateWithFlags(&ctx->c.stream, hipStreamNonBlocking));
-        HIPCHECK(hipEventCreate(&ctx->c.ev0));
-        HIPCHECK(hipEventCreate(&ctx->c.ev1));
+        ctx_create_streams(ctx->c);
         *out = ctx;
     });
 }
@@ -442,6 +289,7 @@ static void ctx_release(Ctx &c) {
     if (c.scratch_index) index_free(c.scratch_index);
     c.scratch_index = nullptr;
     for (auto &s : c.slot) s.release();
+    c.chk.release();
     c.lb_ticket.release();
     for (auto &h : c.host) h.release();
     c.mbox.release();
@@ -457,9 +305,7 @@ static Ctx &scan_lane(Ctx &c, size_t k) {
     while (c.lanes.size() < k) {
         auto l = std::make_unique<Ctx>();
         l->device = c.device;
-        HIPCHECK(hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
-        HIPCHECK(hipEventCreate(&l->ev0));
-        HIPCHECK(hipEventCreate(&l->ev1));
+        ctx_create_streams(*l);
         c.lanes.push_back(std::move(l));
     }
     Ctx &l = *c.lanes[k - 1];
@@ -578,10 +424,7 @@ int bwtmi_strict_scan(bwtmi_ctx *ctx, const uint8_t *seq, int64_t n, int32_t min
         else
             strict_scan_device(c, c.slot[S_TEXT].as<uint8_t>(), n, min_unit, max_unit, min_copies, r);
         *nhits = (int64_t)r.hits.size();
-        auto *out = (bwtmi_hit *)std::malloc(std::max<size_t>(1, r.hits.size()) * sizeof(bwtmi_hit));
-        if (!out) fail(BWTMI_E_NOMEM, "malloc");
-        if (!r.hits.empty()) std::memcpy(out, r.hits.data(), r.hits.size() * sizeof(bwtmi_hit));
-        *hits = out;
+        *hits = malloc_copy(r.hits);
     });
 }
 
@@ -681,10 +524,7 @@ int bwtmi_index_lcp_plateaus(bwtmi_ctx *ctx, bwtmi_index *idx, const bwtmi_lib_p
         use(ctx->c);
         std::vector<int64_t> v;
         lcp_plateaus_device(ctx->c, idx->d, lib_params(p), v);
-        auto *o = (int64_t *)std::malloc(std::max<size_t>(1, v.size()) * sizeof(int64_t));
-        if (!o) fail(BWTMI_E_NOMEM, "malloc");
-        if (!v.empty()) std::memcpy(o, v.data(), v.size() * sizeof(int64_t));
-        *out = o;
+        *out = malloc_copy(v);
         *n = (int64_t)(v.size() / 3);
     });
 }
@@ -839,12 +679,7 @@ struct DevLoad final : FastaDev {
     void contigs() override {
         JobDev &d = job->dev;
         const Job &J = job->j;
-        if (d.device >= 0 && d.device != c.device) {
-            for (auto &s : d.seqs) s.buf.release();
-            d.seqs.clear();
-        }
-        d.device = c.device;
-        d.seqs.resize(J.contigs.size());
+        d.rebind(c.device, J.contigs.size());
         for (size_t i = 0; i < J.contigs.size(); ++i) {
             const Contig &ct = J.contigs[i];
             DevContig &dc = d.seqs[i];
@@ -905,8 +740,7 @@ int bwtmi_job_load_fasta_dev(bwtmi_ctx *ctx, bwtmi_job *job, const char *path, i
         CHECK_ARG(ctx && job && path, "null argument");
         Ctx &c = ctx->c;
         job->j.text_join();
-        if (job->dev.bg_ctx && job->dev.bg_ctx != &c) ctx_wait(*job->dev.bg_ctx);   // it reads the old buffers
-        use(c);
+        job_use(c, job);   // (another context's builds read the old buffers)
         device_wake(c);
         DevLoad dl(c, job);
         load_fasta(job->j, path, flank_trim, 1, 0, &dl);
@@ -946,10 +780,7 @@ int bwtmi_job_fasta_scan_part(bwtmi_job *job, const char *path, int32_t world, i
         TEXT_JOIN(job);
         std::vector<int64_t> v;
         fasta_scan_part(job->j, path, world, rank, v);
-        auto *o = (int64_t *)std::malloc(std::max<size_t>(1, v.size()) * sizeof(int64_t));
-        if (!o) fail(BWTMI_E_NOMEM, "malloc");
-        std::memcpy(o, v.data(), v.size() * sizeof(int64_t));
-        *blob = o;
+        *blob = malloc_copy(v);
         *nwords = (int64_t)v.size();
     });
 }
@@ -965,8 +796,7 @@ int bwtmi_job_fasta_scan_part_dev(bwtmi_ctx *ctx, bwtmi_job *job, const char *pa
         CHECK_ARG(ctx && job && path && blob && nwords && world >= 1 && rank >= 0 && rank < world, "bad argument");
         TEXT_JOIN(job);
         Ctx &c = ctx->c;
-        if (job->dev.bg_ctx && job->dev.bg_ctx != &c) ctx_wait(*job->dev.bg_ctx);
-        use(c);
+        job_use(c, job);
         // the previous part's copy (if any, on whichever context) has left
         // job->j.part before pass 1 overwrites it (fasta_scan_part settles it)
         std::vector<int64_t> v;
@@ -988,10 +818,7 @@ int bwtmi_job_fasta_scan_part_dev(bwtmi_ctx *ctx, bwtmi_job *job, const char *pa
             c.fasta_tag = tag;
             job->j.part_dev_tag = tag;
         }
-        auto *o = (int64_t *)std::malloc(std::max<size_t>(1, v.size()) * sizeof(int64_t));
-        if (!o) fail(BWTMI_E_NOMEM, "malloc");
-        std::memcpy(o, v.data(), v.size() * sizeof(int64_t));
-        *blob = o;
+        *blob = malloc_copy(v);
         *nwords = (int64_t)v.size();
     });
 }
@@ -1013,8 +840,7 @@ int bwtmi_job_load_fasta_parts_dev(bwtmi_ctx *ctx, bwtmi_job *job, const char *p
                   "bad argument");
         Ctx &c = ctx->c;
         job->j.text_join();
-        if (job->dev.bg_ctx && job->dev.bg_ctx != &c) ctx_wait(*job->dev.bg_ctx);
-        use(c);
+        job_use(c, job);
         device_wake(c);
         DevLoad dl(c, job);
         fasta_load_parts(job->j, path, flank_trim, world, rank, blob, nwords, &dl);
@@ -1089,15 +915,9 @@ int bwtmi_job_contig_seq(const bwtmi_job *job, int32_t id, uint8_t *dst) {
 
 static void job_upload(bwtmi_ctx *ctx, bwtmi_job *job) {
     Ctx &c = ctx->c;
-    if (job->dev.bg_ctx && job->dev.bg_ctx != &c) ctx_wait(*job->dev.bg_ctx);
-    use(c);
+    job_use(c, job);
     JobDev &d = job->dev;
-    if (d.device >= 0 && d.device != c.device) {
-        for (auto &s : d.seqs) s.buf.release();
-        d.seqs.clear();
-    }
-    d.device = c.device;
-    d.seqs.resize(job->j.contigs.size());
+    d.rebind(c.device, job->j.contigs.size());
     for (size_t i = 0; i < job->j.contigs.size(); ++i) {
         const Contig &ct = job->j.contigs[i];
         DevContig &dc = d.seqs[i];
@@ -1160,6 +980,197 @@ int bwtmi_job_select(bwtmi_job *job, const int32_t *ids, int32_t n) {
     });
 }
 
+// ------------------------------------------------------------ scan
+extern "C++" {
+namespace {
+using DevText = std::pair<const uint8_t *, int64_t>;   // a contig's device copy and its length
+
+// what one bwtmi_job_scan does (scan_plan)
+struct ScanPlan {
+    std::vector<size_t> todo;         // contigs to scan
+    std::vector<DevText> to_index;    // contigs to index
+    std::vector<int32_t> unit_size;   // contigs per fold unit
+    // nested suppression + sort + dedup on the device (BWTMI_HOST_SCREEN=1: on the host)
+    bool screen = knob(KN_HOST_SCREEN) == 0;
+    const char *fail_contig = std::getenv("BWTMI_FAIL_CONTIG");   // test hook: this contig's worker fails
+    const char *fail_kind = std::getenv("BWTMI_FAIL_KIND");       // "hip": as a device fault
+};
+
+// The job's last results are cleared; which of its (uploaded) contigs are
+// scanned and indexed, and the sizes of their fold units.
+ScanPlan scan_plan(bwtmi_job *job) {
+    Job &J = job->j;
+    J.hits.assign(J.contigs.size(), {});
+    J.screened.assign(J.contigs.size(), 0);
+    J.shits.assign(J.contigs.size(), {});
+    J.raw_n.assign(J.contigs.size(), 0);
+    J.errors.assign(J.contigs.size(), std::string());
+    J.final_recs.clear();
+    J.postprocessed = false;
+    ScanPlan plan;
+    const bwtmi_params &P = J.params;
+    for (size_t i = 0; i < J.contigs.size(); ++i) {
+        const int64_t len = J.contigs[i].trimmed_len();
+        if (!J.selected.empty() && !J.selected[i]) continue;   // another rank's shard
+        if (P.build_index) plan.to_index.push_back({job->dev.seqs[i].buf.as<uint8_t>(), len});
+        if (!P.tier2) continue;                                  // bwt.py:3068
+        if (len > 50000000 && !P.show_progress) continue;        // bwt.py:3070
+        if (P.min_copies <= 0) continue;                         // worker raises -> [] (bwt.py:3137)
+        plan.todo.push_back(i);
+    }
+    // the screen drops hits only the final filter would see (nested.hip) for a
+    // contig that is a fold unit of its own: in a unit of several contigs the
+    // records interleave by position, and another contig's record between two
+    // breaks their merge chain (bwt.py:3222-3289)
+    J.assign_units();
+    plan.unit_size.assign((size_t)std::max<int32_t>(1, J.nunits), 0);
+    for (const Contig &ct : J.contigs) ++plan.unit_size[(size_t)ct.unit];
+    return plan;
+}
+
+// the strict scan of contig i on context lc (c or one of its lanes)
+void scan_contig(Ctx &lc, bwtmi_job *job, const ScanPlan &plan, size_t i) {
+    Job &J = job->j;
+    const bwtmi_params &P = J.params;
+    const Contig &ct = J.contigs[i];
+    const int64_t len = ct.trimmed_len();
+    const int64_t U = std::max<int64_t>(P.max_unit_len, std::min<int64_t>(len / P.min_copies, 1000));
+    // a contig with Tier 3 records is screened on the host, together with them
+    const bool t3 = i < J.t3.size() && !J.t3[i].empty();
+    ScanResult r;
+    // a failing contig yields no records and an error message, the others go on
+    // (the worker's `except Exception: print(...); return []`, bwt.py:3137-3141)
+    // A device fault (BWTMI_E_HIP: a failed launch, copy or synchronisation) is
+    // not contig-local -- the lanes share one device, and a sticky fault fails
+    // every later contig -- and the reference has no such failure: the scan
+    // stops and the call returns the error, so the run fails instead of
+    // writing a partial repeat.tab.
+    try {
+        if (plan.fail_contig && ct.name == plan.fail_contig)
+            fail(plan.fail_kind && !std::strcmp(plan.fail_kind, "hip") ? BWTMI_E_HIP : BWTMI_E_STATE,
+                 "injected failure (BWTMI_FAIL_CONTIG)");
+        strict_scan_device(lc, job->dev.seqs[i].buf.as<uint8_t>(), len, 1, (int32_t)std::min<int64_t>(U, INT32_MAX),
+                           P.min_copies, r, plan.screen && !t3 && len < (int64_t)UINT32_MAX,   // 32-bit hit lengths
+                           plan.unit_size[(size_t)ct.unit] == 1 ? P.min_copies : 0);
+    } catch (const Error &e) {
+        if (e.code == BWTMI_E_HIP) throw;
+        J.errors[i] = e.msg;
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(lc.stream);
+        return;
+    } catch (const std::bad_alloc &) {
+        J.errors[i] = "out of host memory";
+        return;
+    }
+    J.hits[i].swap(r.hits);   // Rule 1 (bwt.py:3118-3130) never fires on strict hits
+    J.shits[i].swap(r.shits);
+    J.screened[i] = r.screened ? 1 : 0;
+    J.raw_n[i] = r.raw;
+}
+
+// one index build on context x (its own stream, slots and scratch index)
+void index_contig(Ctx &x, const DevText &tx, int32_t sa_sample) {
+    const int64_t len = tx.second;
+    // (S_CAND_K2 is free after the scan; index_build_device uses the MISC/IDX slots)
+    DBuf &tb = x.slot[S_CAND_K2];
+    tb.ensure((size_t)len + 1 + 128);
+    HIPCHECK(hipMemcpyAsync(tb.p, tx.first, (size_t)len, hipMemcpyDeviceToDevice, x.stream));
+    HIPCHECK(hipMemsetAsync(tb.as<uint8_t>() + len, '$', 1, x.stream));
+    HIPCHECK(hipMemsetAsync(tb.as<uint8_t>() + len + 1, 0, 127, x.stream));
+    x.scratch_index = index_build_device(x, tb.as<uint8_t>(), len + 1, sa_sample, 128, 0u, x.scratch_index);
+}
+
+size_t lanes_knob(Knob k) { return (size_t)std::clamp<int64_t>(knob(k), 1, 8); }
+
+// The device lanes of c: fn(lane, i) for every item i < weights.size(), on nl
+// contexts at once -- lane 0 is c on the calling thread, lane k >= 1 a context
+// of its own (scan_lane: own stream and scratch) driven by its own host thread.
+// A contig's scan or index build is a chain of small dependent launches and
+// host reads, so one stream leaves the device idle between them.  Items go to
+// lanes by lpt_assign and run longest first.  Every thread is joined before the
+// first error (in lane order) is rethrown; a lane stops at its first error.
+// At most one lane per item; one lane: the items in their order on c, no threads.
+template <class F>
+void run_lanes(Ctx &c, size_t nl, const std::vector<int64_t> &weights, F &&fn) {
+    nl = std::min(nl, weights.size());
+    if (nl <= 1) {
+        for (size_t i = 0; i < weights.size(); ++i) fn(c, i);
+        return;
+    }
+    const std::vector<size_t> owner = lpt_assign(weights, nl);
+    std::vector<std::vector<size_t>> part(nl);
+    for (size_t i = 0; i < owner.size(); ++i) part[owner[i]].push_back(i);
+    for (auto &p : part)
+        std::stable_sort(p.begin(), p.end(), [&](size_t x, size_t y) { return weights[x] > weights[y]; });
+    std::vector<Ctx *> lc(nl);
+    lc[0] = &c;
+    for (size_t k = 1; k < nl; ++k) lc[k] = &scan_lane(c, k);
+    std::vector<std::exception_ptr> ex(nl);
+    auto run = [&](size_t k) {
+        try {
+            if (k) lc[k]->activate();
+            for (size_t i : part[k]) fn(*lc[k], i);
+        } catch (...) {
+            ex[k] = std::current_exception();
+        }
+    };
+    std::vector<std::thread> th;
+    for (size_t k = 1; k < nl; ++k) th.emplace_back(run, k);
+    run(0);
+    for (auto &t : th) t.join();
+    for (size_t k = 1; k < nl; ++k) c.absorb_kstats(*lc[k]);
+    for (auto &e : ex)
+        if (e) std::rethrow_exception(e);
+}
+
+// BWTCore(seq + '$') of the worker (bwt.py:3053-3054).  The worker never consumes
+// it, so the builds run on the background thread c.bg behind the
+// host post-processing.  The scratch index keeps its buffers between builds.
+//
+// Who may touch the context: while c.bg runs it owns c.stream, c.slot[],
+// c.scratch_index, c.kstats / c.pending and every lane of c.  Every entry point
+// reaches a context through use(), which joins c.bg first (ctx_wait) and
+// rethrows its error.  job->dev.bg_ctx and c.bg_link are the two ends of one
+// link -- the job names the context whose builds read its device buffers, the
+// context names that job field -- so that either may end first: the job joins
+// the context before it frees the buffers (bwtmi_job_free, job_use from
+// another context), and the context's join clears the job's field (ctx_join).
+void start_index_builds(Ctx &c, bwtmi_job *job, std::vector<DevText> to_index) {
+    const int32_t sa_sample = job->j.params.sa_sample;
+    c.bg_ms = 0;
+    job->dev.bg_ctx = &c;
+    c.bg_link = &job->dev.bg_ctx;
+    c.bg = std::thread([&c, sa_sample, to_index = std::move(to_index)] {
+        BWTMI_STAGE("bwtmi:index");
+        auto ti = std::chrono::steady_clock::now();
+        try {
+            c.activate();
+            // several contigs: the builds go to the lanes, each lane's builds on its
+            // own stream and host thread -- a 12.5 Mbp build leaves the device mostly
+            // idle, and eight of them in a row outlasted the host stages of the
+            // 8-contig step (C4: 35 ms, r04final)
+            const size_t nl = std::min<size_t>(lanes_knob(KN_INDEX_LANES), to_index.size());
+            std::vector<int64_t> len;
+            for (const DevText &tx : to_index) len.push_back(tx.second);
+            run_lanes(c, nl, len, [&](Ctx &x, size_t i) { index_contig(x, to_index[i], sa_sample); });
+            HIPCHECK(hipStreamSynchronize(c.stream));   // every lane's last build is done
+            for (size_t k = 1; k < nl; ++k) HIPCHECK(hipStreamSynchronize(c.lanes[k - 1]->stream));
+        } catch (const Error &e) {
+            c.bg_code = e.code;
+            c.bg_err = "background index build: " + e.msg;
+        } catch (const std::bad_alloc &) {
+            c.bg_code = BWTMI_E_NOMEM;
+            c.bg_err = "background index build: out of host memory";
+        } catch (const std::exception &e) {
+            c.bg_code = BWTMI_E_STATE;
+            c.bg_err = std::string("background index build: ") + e.what();
+        }
+        c.bg_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ti).count();
+    });
+}
+}  // namespace
+}  // extern "C++"
+
 int bwtmi_job_scan(bwtmi_ctx *ctx, bwtmi_job *job) {
     return guard([&] {
         BWTMI_STAGE("bwtmi:scan");
@@ -1169,203 +1180,17 @@ int bwtmi_job_scan(bwtmi_ctx *ctx, bwtmi_job *job) {
         job_upload(ctx, job);
         Job &J = job->j;
         Ctx &c = ctx->c;
-        J.hits.assign(J.contigs.size(), {});
-        J.screened.assign(J.contigs.size(), 0);
-        J.shits.assign(J.contigs.size(), {});
-        J.raw_n.assign(J.contigs.size(), 0);
-        J.errors.assign(J.contigs.size(), std::string());
-        const char *fail_contig = std::getenv("BWTMI_FAIL_CONTIG");   // test hook: this contig's worker fails
-        const char *fail_kind = std::getenv("BWTMI_FAIL_KIND");       // "hip": as a device fault
-        // nested suppression + sort + dedup on the device (BWTMI_HOST_SCREEN=1: on the host)
-        const bool screen = knob(KN_HOST_SCREEN) == 0;
-        J.final_recs.clear();
-        J.postprocessed = false;
-        const bwtmi_params &P = J.params;
-        std::vector<std::pair<const uint8_t *, int64_t>> to_index;
-        std::vector<size_t> todo;   // contigs to scan
-        for (size_t i = 0; i < J.contigs.size(); ++i) {
-            const Contig &ct = J.contigs[i];
-            const int64_t len = ct.trimmed_len();
-            if (!J.selected.empty() && !J.selected[i]) continue;   // another rank's shard
-            if (P.build_index) to_index.push_back({job->dev.seqs[i].buf.as<uint8_t>(), len});
-            if (!P.tier2) continue;                                  // bwt.py:3068
-            if (len > 50000000 && !P.show_progress) continue;        // bwt.py:3070
-            if (P.min_copies <= 0) continue;                         // worker raises -> [] (bwt.py:3137)
-            todo.push_back(i);
-        }
-        // the screen drops hits only the final filter would see (nested.hip) for a
-        // contig that is a fold unit of its own: in a unit of several contigs the
-        // records interleave by position, and another contig's record between two
-        // breaks their merge chain (bwt.py:3222-3289)
-        J.assign_units();
-        std::vector<int32_t> unit_size((size_t)std::max<int32_t>(1, J.nunits), 0);
-        for (const Contig &ct : J.contigs) ++unit_size[(size_t)ct.unit];
-        auto scan_one = [&](Ctx &lc, size_t i) {
-            const Contig &ct = J.contigs[i];
-            const int64_t len = ct.trimmed_len();
-            const int64_t U = std::max<int64_t>(P.max_unit_len, std::min<int64_t>(len / P.min_copies, 1000));
-            // a contig with Tier 3 records is screened on the host, together with them
-            const bool t3 = i < J.t3.size() && !J.t3[i].empty();
-            ScanResult r;
-            // a failing contig yields no records and an error message, the others go on
-            // (the worker's `except Exception: print(...); return []`, bwt.py:3137-3141)
-            // A device fault (BWTMI_E_HIP: a failed launch, copy or synchronisation) is
-            // not contig-local -- the lanes share one device, and a sticky fault fails
-            // every later contig -- and the reference has no such failure: the scan
-            // stops and the call returns the error, so the run fails instead of
-            // writing a partial repeat.tab.
-            try {
-                if (fail_contig && ct.name == fail_contig)
-                    fail(fail_kind && !std::strcmp(fail_kind, "hip") ? BWTMI_E_HIP : BWTMI_E_STATE,
-                         "injected failure (BWTMI_FAIL_CONTIG)");
-                strict_scan_device(lc, job->dev.seqs[i].buf.as<uint8_t>(), len, 1,
-                                   (int32_t)std::min<int64_t>(U, INT32_MAX), P.min_copies, r,
-                                   screen && !t3 && len < (int64_t)UINT32_MAX,   // 32-bit hit lengths
-                                   unit_size[(size_t)ct.unit] == 1 ? P.min_copies : 0);
-            } catch (const Error &e) {
-                if (e.code == BWTMI_E_HIP) throw;
-                J.errors[i] = e.msg;
-                (void)hipGetLastError();
-                (void)hipStreamSynchronize(lc.stream);
-                return;
-            } catch (const std::bad_alloc &) {
-                J.errors[i] = "out of host memory";
-                return;
-            }
-            J.hits[i].swap(r.hits);   // Rule 1 (bwt.py:3118-3130) never fires on strict hits
-            J.shits[i].swap(r.shits);
-            J.screened[i] = r.screened ? 1 : 0;
-            J.raw_n[i] = r.raw;
-        };
-        // several contigs: up to kLanes scans in flight, each lane a context with
-        // its own stream and scratch driven by its own host thread (a contig's
-        // scan is a chain of small dependent launches and host reads, so one
-        // stream leaves the device idle between them); contigs go to lanes
-        // longest first, each to the least loaded lane
-        const int kLanes = (int)std::max<int64_t>(1, std::min<int64_t>(8, knob(KN_SCAN_LANES)));
-        const size_t nl = std::min<size_t>((size_t)kLanes, todo.size());
-        if (nl <= 1) {
-            for (size_t i : todo) scan_one(c, i);
-        } else {
-            std::vector<size_t> ord(todo);
-            std::stable_sort(ord.begin(), ord.end(), [&](size_t x, size_t y) {
-                return J.contigs[x].trimmed_len() > J.contigs[y].trimmed_len();
-            });
-            std::vector<std::vector<size_t>> part(nl);
-            std::vector<int64_t> load(nl, 0);
-            for (size_t i : ord) {
-                const size_t k = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
-                part[k].push_back(i);
-                load[k] += J.contigs[i].trimmed_len();
-            }
-            std::vector<Ctx *> lc(nl);
-            lc[0] = &c;
-            for (size_t k = 1; k < nl; ++k) lc[k] = &scan_lane(c, k);
-            std::vector<std::exception_ptr> ex(nl);
-            std::vector<std::thread> th;
-            for (size_t k = 1; k < nl; ++k)
-                th.emplace_back([&, k] {
-                    try {
-                        lc[k]->activate();
-                        for (size_t i : part[k]) scan_one(*lc[k], i);
-                    } catch (...) {
-                        ex[k] = std::current_exception();
-                    }
-                });
-            try {
-                for (size_t i : part[0]) scan_one(c, i);
-            } catch (...) {
-                ex[0] = std::current_exception();
-            }
-            for (auto &t : th) t.join();
-            for (size_t k = 1; k < nl; ++k) c.absorb_kstats(*lc[k]);
-            for (auto &e : ex)
-                if (e) std::rethrow_exception(e);
-        }
+        ScanPlan plan = scan_plan(job);
+        // several contigs: up to BWTMI_SCAN_LANES scans in flight (run_lanes)
+        std::vector<int64_t> len;
+        for (size_t i : plan.todo) len.push_back(J.contigs[i].trimmed_len());
+        run_lanes(c, lanes_knob(KN_SCAN_LANES), len,
+                  [&](Ctx &lc, size_t k) { scan_contig(lc, job, plan, plan.todo[k]); });
         J.text_join();   // the host copies written behind this scan (bwtmi_job_load_fasta_dev)
         J.stage_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         J.stage_ms[1] = 0;
-        if (to_index.empty()) return;
-        // BWTCore(seq + '$') of the worker (bwt.py:3053-3054). The worker never consumes
-        // it, so the builds run on a background thread behind the host
-        // post-processing; every later use of this ctx (or of this job's device
-        // buffers) joins them first. The scratch index keeps its buffers between builds.
-        const int32_t sa_sample = P.sa_sample;
-        c.bg_ms = 0;
-        job->dev.bg_ctx = &c;
-        c.bg_link = &job->dev.bg_ctx;
-        c.bg = std::thread([&c, sa_sample, to_index] {
-            BWTMI_STAGE("bwtmi:index");
-            auto ti = std::chrono::steady_clock::now();
-            try {
-                c.activate();
-                // one build on context x (its own stream, slots and scratch index)
-                auto build = [sa_sample](Ctx &x, const std::pair<const uint8_t *, int64_t> &tx) {
-                    const int64_t len = tx.second;
-                    // (S_CAND_K2 is free after the scan; index_build_device uses the MISC/IDX slots)
-                    DBuf &tb = x.slot[S_CAND_K2];
-                    tb.ensure((size_t)len + 1 + 128);
-                    HIPCHECK(hipMemcpyAsync(tb.p, tx.first, (size_t)len, hipMemcpyDeviceToDevice, x.stream));
-                    HIPCHECK(hipMemsetAsync(tb.as<uint8_t>() + len, '$', 1, x.stream));
-                    HIPCHECK(hipMemsetAsync(tb.as<uint8_t>() + len + 1, 0, 127, x.stream));
-                    x.scratch_index = index_build_device(x, tb.as<uint8_t>(), len + 1, sa_sample, 128, 0u,
-                                                         x.scratch_index);
-                };
-                // several contigs: the builds go to the scan lanes (longest first, each
-                // to the least loaded lane), each lane's builds on its own stream and
-                // host thread -- a 12.5 Mbp build is a chain of small launches and host
-                // reads that leaves the device mostly idle, and eight of them in a row
-                // outlasted the host stages of the 8-contig step (C4: 35 ms, r04final)
-                const int kIndexLanes = (int)std::max<int64_t>(1, std::min<int64_t>(8, knob(KN_INDEX_LANES)));
-                const size_t nl = std::min<size_t>((size_t)kIndexLanes, to_index.size());
-                if (nl <= 1) {
-                    for (const auto &tx : to_index) build(c, tx);
-                    HIPCHECK(hipStreamSynchronize(c.stream));
-                } else {
-                    std::vector<size_t> ord(to_index.size());
-                    for (size_t i = 0; i < ord.size(); ++i) ord[i] = i;
-                    std::stable_sort(ord.begin(), ord.end(),
-                                     [&](size_t x, size_t y) { return to_index[x].second > to_index[y].second; });
-                    std::vector<std::vector<size_t>> part(nl);
-                    std::vector<int64_t> load(nl, 0);
-                    for (size_t i : ord) {
-                        const size_t k = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
-                        part[k].push_back(i);
-                        load[k] += to_index[i].second;
-                    }
-                    std::vector<Ctx *> lc(nl);
-                    lc[0] = &c;
-                    for (size_t k = 1; k < nl; ++k) lc[k] = &scan_lane(c, k);
-                    std::vector<std::exception_ptr> ex(nl);
-                    auto run = [&](size_t k) {
-                        try {
-                            if (k) lc[k]->activate();
-                            for (size_t i : part[k]) build(*lc[k], to_index[i]);
-                            HIPCHECK(hipStreamSynchronize(lc[k]->stream));
-                        } catch (...) {
-                            ex[k] = std::current_exception();
-                        }
-                    };
-                    std::vector<std::thread> th;
-                    for (size_t k = 1; k < nl; ++k) th.emplace_back(run, k);
-                    run(0);
-                    for (auto &t : th) t.join();
-                    for (size_t k = 1; k < nl; ++k) c.absorb_kstats(*lc[k]);
-                    for (auto &e : ex)
-                        if (e) std::rethrow_exception(e);
-                }
-            } catch (const Error &e) {
-                c.bg_code = e.code;
-                c.bg_err = "background index build: " + e.msg;
-            } catch (const std::bad_alloc &) {
-                c.bg_code = BWTMI_E_NOMEM;
-                c.bg_err = "background index build: out of host memory";
-            } catch (const std::exception &e) {
-                c.bg_code = BWTMI_E_STATE;
-                c.bg_err = std::string("background index build: ") + e.what();
-            }
-            c.bg_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ti).count();
-        });
+        // every later use of this ctx (or of this job's device buffers) joins the builds first
+        if (!plan.to_index.empty()) start_index_builds(c, job, std::move(plan.to_index));
     });
 }
 
@@ -1533,7 +1358,7 @@ int bwtmi_job_write_units(bwtmi_job *job, const char *path, const int64_t *offse
         std::vector<Text> parts;
         std::vector<size_t> at;
         units_parts(job, offsets, write_header, parts, at);
-        pwrite_parts(path, false, parts, at, host_threads(job->j.params));
+        pwrite_parts(path, false, parts, at);
     });
 }
 
@@ -1549,10 +1374,9 @@ int bwtmi_job_write_units_async(bwtmi_job *job, const char *path, const int64_t 
         std::vector<Text> parts;
         std::vector<size_t> at;
         units_parts(job, offsets, write_header, parts, at);
-        const int nt = host_threads(job->j.params);
-        job->units_wr = std::thread([job, p = std::string(path), parts = std::move(parts), at = std::move(at), nt] {
+        job->units_wr = std::thread([job, p = std::string(path), parts = std::move(parts), at = std::move(at)] {
             try {
-                pwrite_parts(p.c_str(), false, parts, at, nt);
+                pwrite_parts(p.c_str(), false, parts, at);
             } catch (...) {
                 job->units_err = std::current_exception();
             }

@@ -3,6 +3,7 @@
 
 #include <sched.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <cstring>
@@ -424,8 +425,24 @@ void load_fasta(Job &job, const char *path, int32_t flank_trim, int32_t world = 
 void fasta_scan_part(Job &job, const char *path, int32_t world, int32_t rank, std::vector<int64_t> &blob);
 void fasta_load_parts(Job &job, const char *path, int32_t flank_trim, int32_t world, int32_t rank,
                       const int64_t *blob, int64_t nwords, FastaDev *dev = nullptr);
-// fold units -> ranks by longest-processing-time greedy (deterministic; same as
-// bwtmi.dist.assign): returns the contig ids owned by `rank`
+// longest-processing-time greedy: items by descending weight (stable), each to
+// the least loaded bin, ties to the lowest bin (deterministic; the rule of
+// bwtmi.dist.assign).  Returns each item's bin.  Used for fold units -> ranks
+// (shard_units) and contigs -> device lanes (api.cpp run_lanes); defined here
+// so that a stand-alone program can check it (tools/outfile_check.cpp).
+inline std::vector<size_t> lpt_assign(const std::vector<int64_t> &weights, size_t bins) {
+    std::vector<size_t> order(weights.size()), owner(weights.size(), 0);
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return weights[a] > weights[b]; });
+    std::vector<int64_t> load(std::max<size_t>(1, bins), 0);
+    for (size_t i : order) {
+        owner[i] = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
+        load[owner[i]] += weights[i];
+    }
+    return owner;
+}
+// fold units -> ranks by lpt_assign over the units' analysed lengths: returns
+// the contig ids owned by `rank`
 std::vector<int32_t> shard_units(Job &job, int32_t world, int32_t rank);
 
 // host threads of one process: params.threads, else this process's share of

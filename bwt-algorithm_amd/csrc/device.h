@@ -100,6 +100,15 @@ struct KStat {
     int64_t launches = 0;
     double bytes = 0;   // algorithmic bytes (compulsory reads + writes) of those launches
 };
+using KStats = std::vector<std::pair<std::string, KStat>>;   // in order of first launch
+// `launches` launches of kernel `name` added to its entry (appended when new)
+inline void kstat_add(KStats &kstats, const std::string &name, double ms, int64_t launches, double bytes) {
+    auto it = std::find_if(kstats.begin(), kstats.end(), [&](const auto &k) { return k.first == name; });
+    if (it == kstats.end()) it = kstats.insert(it, {name, KStat{}});
+    it->second.ms += ms;
+    it->second.launches += launches;
+    it->second.bytes += bytes;
+}
 
 struct Ctx {
     int device = 0;
@@ -119,7 +128,7 @@ struct Ctx {
     // bwtmi_kernel_stats_filter: time only the launches of this name ("" = every
     // launch); the others get no events, so they run back to back as untimed
     std::string kfilter;
-    std::vector<std::pair<std::string, KStat>> kstats;
+    KStats kstats;
     std::vector<hipEvent_t> evpool;   // reused across kresolve calls
     size_t evused = 0;
     hipEvent_t pooled_event() {
@@ -174,16 +183,7 @@ struct Ctx {
                 }
                 std::fprintf(trace, "%s %.4f %.4f\n", p.name.c_str(), ms, gap);
             }
-            bool found = false;
-            for (auto &k : kstats)
-                if (k.first == p.name) {
-                    k.second.ms += ms;
-                    ++k.second.launches;
-                    k.second.bytes += p.bytes;
-                    found = true;
-                    break;
-                }
-            if (!found) kstats.push_back({p.name, KStat{ms, 1, p.bytes}});
+            kstat_add(kstats, p.name, ms, 1, p.bytes);
         }
         if (trace) {
             std::fprintf(trace, "-- resolve\n");
@@ -241,18 +241,7 @@ struct Ctx {
     void activate() const { HIPCHECK(hipSetDevice(device)); }
     // per-kernel statistics of another context (a lane) folded into this one
     void absorb_kstats(Ctx &o) {
-        for (auto &k : o.kstats) {
-            bool found = false;
-            for (auto &m : kstats)
-                if (m.first == k.first) {
-                    m.second.ms += k.second.ms;
-                    m.second.launches += k.second.launches;
-                    m.second.bytes += k.second.bytes;
-                    found = true;
-                    break;
-                }
-            if (!found) kstats.push_back(k);
-        }
+        for (auto &k : o.kstats) kstat_add(kstats, k.first, k.second.ms, k.second.launches, k.second.bytes);
         o.kstats.clear();
     }
 };
@@ -266,7 +255,6 @@ struct Ctx {
         c.kend();                                                              \
     } while (0)
 
-// join the context's background device work; rethrows its error
 // The scan's host reads (candidate counts, key widths, hit counts) wait on the
 // stream by polling: a blocking wait (hipDeviceScheduleBlockingSync, kept for
 // the long waits behind host work) sleeps the thread, and its wake-up delays
@@ -285,6 +273,7 @@ inline void ctx_join(Ctx &c) {
     if (c.bg_link) *c.bg_link = nullptr;
     c.bg_link = nullptr;
 }
+// join the context's background device work; rethrows its error
 inline void ctx_wait(Ctx &c) {
     ctx_join(c);
     if (c.bg_code) {

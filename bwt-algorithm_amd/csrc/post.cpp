@@ -510,21 +510,10 @@ std::vector<int32_t> shard_units(Job &job, int32_t world, int32_t rank) {
     job.assign_units();
     std::vector<int64_t> w((size_t)job.nunits, 0);
     for (auto &c : job.contigs) w[(size_t)c.unit] += c.weight;
-    std::vector<int32_t> order((size_t)job.nunits);
-    for (int32_t u = 0; u < job.nunits; ++u) order[(size_t)u] = u;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return w[(size_t)a] > w[(size_t)b]; });
-    std::vector<int64_t> load((size_t)std::max(1, world), 0);
-    std::vector<int32_t> owner((size_t)job.nunits, 0);
-    for (int32_t u : order) {
-        int32_t r = 0;
-        for (int32_t x = 1; x < world; ++x)
-            if (load[(size_t)x] < load[(size_t)r]) r = x;
-        load[(size_t)r] += w[(size_t)u];
-        owner[(size_t)u] = r;
-    }
+    const std::vector<size_t> owner = lpt_assign(w, (size_t)std::max(1, world));
     std::vector<int32_t> out;
     for (size_t c = 0; c < job.contigs.size(); ++c)
-        if (owner[(size_t)job.contigs[c].unit] == rank) out.push_back((int32_t)c);
+        if (owner[(size_t)job.contigs[c].unit] == (size_t)rank) out.push_back((int32_t)c);
     return out;
 }
 

@@ -238,7 +238,7 @@ def test_cli_eight_self_launched_ranks_match_c4_golden(gpu_ctx, golden_dir, tmp_
 
 def test_scan_and_index_lanes_switches(gpu_ctx):
     """A multi-contig job's strict scans and background index builds on 1 lane
-    (BWTMI_SCAN_LANES=1, BWTMI_INDEX_LANES=1) or 8: the same records."""
+    (BWTMI_SCAN_LANES=1, BWTMI_INDEX_LANES=1), 8, or 3 and 2: the same records."""
     from bwtmi import _lib, synth
     from bwtmi.records import Job
     seqs = [synth.generate_contig(150_000 + 40_000 * i, 70 + i, 0.02, gaps="n1" if i % 3 == 0 else None)
@@ -254,7 +254,8 @@ def test_scan_and_index_lanes_switches(gpu_ctx):
         return j.render("strfinder")
     want = run()
     assert want.count(b"\n") > 1000
-    for kv in ({"SCAN_LANES": 1, "INDEX_LANES": 1}, {"SCAN_LANES": 8, "INDEX_LANES": 8}):
+    for kv in ({"SCAN_LANES": 1, "INDEX_LANES": 1}, {"SCAN_LANES": 8, "INDEX_LANES": 8},
+               {"SCAN_LANES": 3, "INDEX_LANES": 2}):   # uneven lanes, another count at each site
         with _lib.knobs(**kv):
             assert run() == want, kv
 

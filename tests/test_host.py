@@ -583,7 +583,10 @@ def _sharded_write_worker(rank, world, port, fa, outdir):
     comm.close()
 
 
-@pytest.mark.parametrize("world,name", [(2, "test_all_12.fa"), (3, "edge_mixed.fa")])
+# (synth_imperfect2.fa: one contig, synth_small.fa: two -- the ranks beyond them
+# own no fold unit and write neither rows nor the header)
+@pytest.mark.parametrize("world,name", [(2, "test_all_12.fa"), (3, "edge_mixed.fa"), (2, "synth_imperfect2.fa"),
+                                        (4, "synth_small.fa")])
 def test_sharded_write_matches_single_process(tmp_path, golden_dir, built_lib, world, name):
     """Each rank writes its own fold units at exchanged offsets; the file equals
     the single-process output in every format (incl. global VCF row ids), also
