@@ -51,6 +51,29 @@ class _LazyText:
         return getattr(self._str(), name)
 
 
+class LocateResult:
+    """Hits of BWTCore.locate_batch: `offsets` (int64[npat + 1]) into `positions`
+    (int64), `mismatches` (uint8) and `strand` (uint8, 0 = '+', 1 = '-');
+    result[i] = the three slices of pattern i, sorted by (position, strand).
+    `candidates` is the call's candidate count (what max_candidates caps)."""
+
+    __slots__ = ("offsets", "positions", "mismatches", "strand", "candidates")
+
+    def __init__(self, offsets, positions, mismatches, strand, candidates=0):
+        self.offsets, self.positions, self.mismatches, self.strand = offsets, positions, mismatches, strand
+        self.candidates = candidates
+
+    def __len__(self):
+        return self.offsets.size - 1
+
+    def __getitem__(self, i: int):
+        if not -len(self) <= i < len(self):
+            raise IndexError(i)
+        i %= len(self)
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        return self.positions[a:b], self.mismatches[a:b], self.strand[a:b]
+
+
 class BWTCore:
     BASE_TO_BITS = {"A": 0, "C": 1, "G": 2, "T": 3, "N": 0}
     BITS_TO_BASE = {0: "A", 1: "C", 2: "G", 3: "T"}
@@ -233,6 +256,48 @@ class BWTCore:
         if sp == -1:
             return []
         return sorted(self.suffix_array[sp:ep + 1].tolist())
+
+    def locate_batch(self, patterns: Sequence[Union[str, bytes]], max_mismatches: int = 0,
+                     both_strands: bool = False, max_candidates: Optional[int] = None) -> "LocateResult":
+        """Every occurrence of every pattern with at most `max_mismatches`
+        (0..3) substitutions, on the text's strand or on both, located on the
+        device (include/bwtmi.h, bwtmi_index_locate_batch, states the contract).
+        ValueError for an empty pattern, one shorter than max_mismatches + 1
+        or longer than 1024 bytes, or max_mismatches outside 0..3; BwtmiError
+        with the candidate count when it exceeds max_candidates (default 2^27)."""
+        if max_candidates is not None and int(max_candidates) <= 0:
+            raise ValueError("max_candidates must be positive")
+        # encoded as pack_patterns does (bytes are taken as they are)
+        enc = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in patterns]
+        off = np.zeros(len(enc) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(e) for e in enc]) if enc else 0
+        blob = np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8)
+        npat = off.size - 1
+        hoff, pos, mm, strand = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nh, cand = C.c_int64(0), C.c_int64(0)
+        rc = lib().bwtmi_index_locate_batch(self._ctx, self._h, blob.ctypes.data_as(C.c_void_p),
+                                            off.ctypes.data_as(C.c_void_p), npat, int(max_mismatches),
+                                            1 if both_strands else 0,
+                                            0 if max_candidates is None else int(max_candidates),
+                                            C.byref(hoff), C.byref(pos), C.byref(mm), C.byref(strand),
+                                            C.byref(nh), C.byref(cand))
+        if rc == -1:   # BWTMI_E_ARG
+            msg = lib().bwtmi_last_error()
+            raise ValueError(msg.decode(errors="replace") if msg else "bad argument")
+        check(rc)
+        try:
+            n = nh.value
+
+            def take(p, dtype, count):
+                if not count:
+                    return np.zeros(0, dtype=dtype)
+                return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))),
+                                             shape=(count,)).copy()
+            return LocateResult(take(hoff, np.int64, npat + 1), take(pos, np.int64, n), take(mm, np.uint8, n),
+                                take(strand, np.uint8, n), cand.value)
+        finally:
+            for p in (hoff, pos, mm, strand):
+                lib().bwtmi_free(p)
 
     def _get_suffix_position(self, sa_index: int) -> int:
         return int(self.suffix_array[sa_index])

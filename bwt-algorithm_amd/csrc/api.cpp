@@ -501,6 +501,35 @@ int bwtmi_backward_search_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t 
     });
 }
 
+int bwtmi_index_locate_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *pats, const int64_t *off, int64_t npat,
+                             int32_t max_mismatch, uint32_t flags, int64_t max_candidates, int64_t **hit_off,
+                             int64_t **pos, uint8_t **mm, uint8_t **strand, int64_t *nhits, int64_t *candidates) {
+    return guard([&] {
+        CHECK_ARG(ctx && idx && off && hit_off && pos && mm && strand && nhits && npat >= 0, "bad argument");
+        CHECK_ARG(pats || npat == 0, "null patterns");
+        *hit_off = *pos = nullptr;
+        *mm = *strand = nullptr;
+        *nhits = 0;
+        if (candidates) *candidates = 0;
+        CHECK_ARG((flags & ~BWTMI_LOCATE_BOTH_STRANDS) == 0, "unknown locate flag");
+        use(ctx->c);
+        LocateResult r;
+        try {
+            index_locate_batch(ctx->c, idx->d, pats, off, npat, max_mismatch, (flags & BWTMI_LOCATE_BOTH_STRANDS) != 0,
+                               max_candidates, r);
+        } catch (...) {
+            if (candidates) *candidates = r.candidates;   // the count a tripped cap reports
+            throw;
+        }
+        if (candidates) *candidates = r.candidates;
+        *hit_off = malloc_copy(r.hit_off);
+        *pos = malloc_copy(r.pos);
+        *mm = malloc_copy(r.mm);
+        *strand = malloc_copy(r.strand);
+        *nhits = (int64_t)r.pos.size();
+    });
+}
+
 static LibParams lib_params(const bwtmi_lib_params *p) {
     LibParams q;
     if (p) {

@@ -295,6 +295,9 @@ constexpr uint32_t kChkDeepEnd = 64;     // a deep suffix whose run end is not i
 // ----- primitives (radix.hip)
 template <class T>
 void exclusive_scan(Ctx &c, const T *in, T *out, int64_t n);   // out may alias in
+// 64-bit sums (interval widths): three plain passes, tile sums in S_SCAN_TMP
+template <>
+void exclusive_scan<int64_t>(Ctx &c, const int64_t *in, int64_t *out, int64_t n);
 // `rows` independent scans of n uint32 each, row r at in / out + r * stride, in one launch
 void exclusive_scan_rows(Ctx &c, const uint32_t *in, uint32_t *out, int64_t n, int rows, int64_t stride);
 void radix_sort_pairs(Ctx &c, uint64_t *keys, uint64_t *vals, int64_t n, int bit0, int bit1);
@@ -412,6 +415,22 @@ void tier1_device(Ctx &c, const uint8_t *d_text, const uint8_t *t, int64_t n, in
 void index_backward_search(Ctx &c, DeviceIndex *, const uint8_t *pats, const int64_t *off, int64_t npat,
                            int64_t *sp_ep);
 void index_sa_rows(Ctx &c, const DeviceIndex *, const int64_t *rows, int64_t k, int64_t *out);
+// exact backward search of np pieces d_pats[d_off[p], d_off[p + 1]) (device arrays, plen bytes
+// in all) with the results left on the device: first SA row and width (0 = absent) per piece
+void index_seed_search_device(Ctx &c, DeviceIndex *, const uint8_t *d_pats, const int64_t *d_off, int64_t np,
+                              int64_t plen, int64_t *d_row0, int64_t *d_width);
+
+// ----- batched locate with mismatches on both strands (locate.hip; contract in bwtmi.h)
+constexpr int kLocMaxMismatch = 3;
+constexpr int64_t kLocMaxPattern = 1024;
+constexpr int64_t kLocDefaultCap = int64_t{1} << 27;
+struct LocateResult {
+    std::vector<int64_t> hit_off, pos;   // npat + 1 offsets; positions
+    std::vector<uint8_t> mm, strand;     // mismatches; 0 = '+', 1 = '-'
+    int64_t candidates = 0;
+};
+void index_locate_batch(Ctx &c, DeviceIndex *ix, const uint8_t *pats, const int64_t *off, int64_t npat,
+                        int32_t max_mismatch, bool both_strands, int64_t max_candidates, LocateResult &out);
 // Tier2LCPFinder.find_long_repeats -> _find_repeats_simple (bwt.py:2097-2106, 2177-2498)
 void simple_scan_device(Ctx &c, DeviceIndex *ix, const LibParams &p, const std::vector<int64_t> &seen_pairs,
                         int32_t chrom, RecVec &out);

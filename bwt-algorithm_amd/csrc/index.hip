@@ -477,33 +477,52 @@ __device__ __forceinline__ int code5(uint8_t ch) {
 }
 
 // backward search over the packed rank, one pattern per lane: each step is
-// two 32-byte block loads and two popcounts
+// two 32-byte block loads and two popcounts.  The lane's search of pats[a, b)
+// (shared by k_bsearch2 and the locate seed search, k_loc_seed2)
+__device__ __forceinline__ void bsearch2_lane(const FM2View &f, const uint8_t *__restrict__ pats, int64_t a, int64_t b,
+                                              int64_t &sp, int64_t &ep) {
+    sp = ep = -1;
+    if (b == a) {
+        sp = 0;
+        ep = f.n - 1;
+        return;
+    }
+    int c = code5(pats[b - 1]);
+    if (c >= 0 && f.tot[c] > 0) {
+        sp = f.C[c];
+        ep = sp + f.tot[c] - 1;
+        for (int64_t i = b - 2; i >= a; --i) {
+            c = code5(pats[i]);
+            if (c < 0 || f.tot[c] == 0) { sp = ep = -1; break; }
+            sp = f.C[c] + rank2(f, c, sp);
+            ep = f.C[c] + rank2(f, c, ep + 1) - 1;
+            if (sp > ep) { sp = ep = -1; break; }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_bsearch2(FM2View f, const uint8_t *__restrict__ pats,
                                                   const int64_t *__restrict__ off, int64_t np,
                                                   int64_t *__restrict__ out) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= np) return;
-    const int64_t a = off[p], b = off[p + 1];
-    int64_t sp = -1, ep = -1;
-    if (b == a) {
-        sp = 0;
-        ep = f.n - 1;
-    } else {
-        int c = code5(pats[b - 1]);
-        if (c >= 0 && f.tot[c] > 0) {
-            sp = f.C[c];
-            ep = sp + f.tot[c] - 1;
-            for (int64_t i = b - 2; i >= a; --i) {
-                c = code5(pats[i]);
-                if (c < 0 || f.tot[c] == 0) { sp = ep = -1; break; }
-                sp = f.C[c] + rank2(f, c, sp);
-                ep = f.C[c] + rank2(f, c, ep + 1) - 1;
-                if (sp > ep) { sp = ep = -1; break; }
-            }
-        }
-    }
+    int64_t sp, ep;
+    bsearch2_lane(f, pats, off[p], off[p + 1], sp, ep);
     out[2 * p] = sp;
     out[2 * p + 1] = ep;
+}
+
+// the locate seed search: the interval's first row and its width (0 = no
+// occurrence) of every piece, left on the device
+__global__ __launch_bounds__(256) void k_loc_seed2(FM2View f, const uint8_t *__restrict__ pats,
+                                                   const int64_t *__restrict__ off, int64_t np,
+                                                   int64_t *__restrict__ row0, int64_t *__restrict__ width) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= np) return;
+    int64_t sp, ep;
+    bsearch2_lane(f, pats, off[p], off[p + 1], sp, ep);
+    row0[p] = sp < 0 ? 0 : sp;
+    width[p] = sp < 0 ? 0 : ep - sp + 1;
 }
 
 // ---- backward search (bwt.py:335-389), one pattern per lane
@@ -526,31 +545,47 @@ __device__ int64_t d_rank(const FMView &f, uint8_t c, int64_t pos) {
     return base;
 }
 
+// the lane's search of pats[a, b) (shared by k_bsearch and k_loc_seed)
+__device__ __forceinline__ void bsearch_lane(const FMView &f, const uint8_t *__restrict__ pats, int64_t a, int64_t b,
+                                             int64_t &sp, int64_t &ep) {
+    sp = ep = -1;
+    if (b == a) {
+        sp = 0;
+        ep = f.n - 1;
+        return;
+    }
+    uint8_t c = pats[b - 1];
+    if (f.tot[c] > 0) {
+        sp = f.C[c];
+        ep = sp + f.tot[c] - 1;
+        for (int64_t i = b - 2; i >= a; --i) {
+            c = pats[i];
+            if (f.tot[c] == 0) { sp = ep = -1; break; }
+            sp = f.C[c] + d_rank(f, c, sp);
+            ep = f.C[c] + d_rank(f, c, ep + 1) - 1;
+            if (sp > ep) { sp = ep = -1; break; }
+        }
+    }
+}
+
 __global__ void k_bsearch(FMView f, const uint8_t *__restrict__ pats, const int64_t *__restrict__ off, int64_t np,
                           int64_t *__restrict__ out) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= np) return;
-    const int64_t a = off[p], b = off[p + 1];
-    int64_t sp = -1, ep = -1;
-    if (b == a) {
-        sp = 0;
-        ep = f.n - 1;
-    } else {
-        uint8_t c = pats[b - 1];
-        if (f.tot[c] > 0) {
-            sp = f.C[c];
-            ep = sp + f.tot[c] - 1;
-            for (int64_t i = b - 2; i >= a; --i) {
-                c = pats[i];
-                if (f.tot[c] == 0) { sp = ep = -1; break; }
-                sp = f.C[c] + d_rank(f, c, sp);
-                ep = f.C[c] + d_rank(f, c, ep + 1) - 1;
-                if (sp > ep) { sp = ep = -1; break; }
-            }
-        }
-    }
+    int64_t sp, ep;
+    bsearch_lane(f, pats, off[p], off[p + 1], sp, ep);
     out[2 * p] = sp;
     out[2 * p + 1] = ep;
+}
+
+__global__ void k_loc_seed(FMView f, const uint8_t *__restrict__ pats, const int64_t *__restrict__ off, int64_t np,
+                           int64_t *__restrict__ row0, int64_t *__restrict__ width) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= np) return;
+    int64_t sp, ep;
+    bsearch_lane(f, pats, off[p], off[p + 1], sp, ep);
+    row0[p] = sp < 0 ? 0 : sp;
+    width[p] = sp < 0 ? 0 : ep - sp + 1;
 }
 
 inline unsigned blocks(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
@@ -927,38 +962,27 @@ void index_sa_rows(Ctx &c, const DeviceIndex *ix, const int64_t *rows, int64_t k
     HIPCHECK(hipStreamSynchronize(st));
 }
 
-void index_backward_search(Ctx &c, DeviceIndex *ix, const uint8_t *pats, const int64_t *off, int64_t npat,
-                           int64_t *sp_ep) {
-    if (npat <= 0) return;
+namespace {
+FM2View fm2_view(const DeviceIndex *ix) {
+    FM2View g;
+    g.blk = ix->fm2.as<uint4>();
+    const char sym[5] = {'A', 'C', 'G', 'T', '$'};
+    for (int q = 0; q < 5; ++q) {
+        g.C[q] = ix->C[(uint8_t)sym[q]];
+        g.tot[q] = ix->totals[(uint8_t)sym[q]];
+    }
+    g.n = ix->n;
+    g.dollar = ix->dollar_row;
+    return g;
+}
+// the byte-Occ view; its C / totals / row tables go up into the S_MISC3 slot
+FMView fm_view(Ctx &c, const DeviceIndex *ix) {
     hipStream_t st = c.stream;
-    const int64_t plen = off[npat];
-    c.slot[S_MISC0].ensure((size_t)plen + 8);
-    c.slot[S_MISC1].ensure((size_t)(npat + 1) * 8);
-    c.slot[S_MISC2].ensure((size_t)npat * 16);
     c.slot[S_MISC3].ensure(256 * 8 * 2 + 256);
-    if (plen) HIPCHECK(hipMemcpyAsync(c.slot[S_MISC0].p, pats, (size_t)plen, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(c.slot[S_MISC1].p, off, (size_t)(npat + 1) * 8, hipMemcpyHostToDevice, st));
     int64_t *tabs = c.slot[S_MISC3].as<int64_t>();
     HIPCHECK(hipMemcpyAsync(tabs, ix->C, 256 * 8, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(tabs + 256, ix->totals, 256 * 8, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(tabs + 512, ix->code_of, 256, hipMemcpyHostToDevice, st));
-    if (ix->has_fm2 && !knob(KN_FM_BYTES)) {
-        FM2View g;
-        g.blk = ix->fm2.as<uint4>();
-        const char sym[5] = {'A', 'C', 'G', 'T', '$'};
-        for (int q = 0; q < 5; ++q) {
-            g.C[q] = ix->C[(uint8_t)sym[q]];
-            g.tot[q] = ix->totals[(uint8_t)sym[q]];
-        }
-        g.n = ix->n;
-        g.dollar = ix->dollar_row;
-        KLAUNCH("k_bsearch2", 0.0, k_bsearch2, dim3(blocks(npat)), dim3(256), 0, st, g, c.slot[S_MISC0].as<uint8_t>(),
-                c.slot[S_MISC1].as<int64_t>(), npat, c.slot[S_MISC2].as<int64_t>());
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpyAsync(sp_ep, c.slot[S_MISC2].p, (size_t)npat * 16, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-        return;
-    }
     FMView f;
     f.bwt = ix->bwt.as<uint8_t>();
     f.occ = ix->occ.as<int32_t>();
@@ -968,11 +992,53 @@ void index_backward_search(Ctx &c, DeviceIndex *ix, const uint8_t *pats, const i
     f.n = ix->n;
     f.olen = index_occ_len(ix);
     f.k = ix->occ_sample;
-    KLAUNCH("k_bsearch", 0.0, k_bsearch, dim3(blocks(npat)), dim3(256), 0, st, f, c.slot[S_MISC0].as<uint8_t>(),
-                       c.slot[S_MISC1].as<int64_t>(), npat, c.slot[S_MISC2].as<int64_t>());
+    return f;
+}
+}  // namespace
+
+void index_backward_search(Ctx &c, DeviceIndex *ix, const uint8_t *pats, const int64_t *off, int64_t npat,
+                           int64_t *sp_ep) {
+    if (npat <= 0) return;
+    hipStream_t st = c.stream;
+    const int64_t plen = off[npat];
+    c.slot[S_MISC0].ensure((size_t)plen + 8);
+    c.slot[S_MISC1].ensure((size_t)(npat + 1) * 8);
+    c.slot[S_MISC2].ensure((size_t)npat * 16);
+    if (plen) HIPCHECK(hipMemcpyAsync(c.slot[S_MISC0].p, pats, (size_t)plen, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(c.slot[S_MISC1].p, off, (size_t)(npat + 1) * 8, hipMemcpyHostToDevice, st));
+    const FMView f = fm_view(c, ix);
+    if (ix->has_fm2 && !knob(KN_FM_BYTES)) {
+        const FM2View g = fm2_view(ix);
+        KLAUNCH("k_bsearch2", 0.0, k_bsearch2, dim3(blocks(npat)), dim3(256), 0, st, g, c.slot[S_MISC0].as<uint8_t>(),
+                c.slot[S_MISC1].as<int64_t>(), npat, c.slot[S_MISC2].as<int64_t>());
+    } else {
+        KLAUNCH("k_bsearch", 0.0, k_bsearch, dim3(blocks(npat)), dim3(256), 0, st, f, c.slot[S_MISC0].as<uint8_t>(),
+                c.slot[S_MISC1].as<int64_t>(), npat, c.slot[S_MISC2].as<int64_t>());
+    }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(sp_ep, c.slot[S_MISC2].p, (size_t)npat * 16, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
+}
+
+// The locate seed search (locate.hip): exact backward search of np pieces,
+// piece p = d_pats[d_off[p], d_off[p + 1]) (device arrays), through the same
+// rank paths as index_backward_search; the first SA row and the width of every
+// interval stay on the device.  Uses the S_MISC3 slot (byte-Occ tables).
+void index_seed_search_device(Ctx &c, DeviceIndex *ix, const uint8_t *d_pats, const int64_t *d_off, int64_t np,
+                              int64_t plen, int64_t *d_row0, int64_t *d_width) {
+    if (np <= 0) return;
+    hipStream_t st = c.stream;
+    // per piece: its bytes and ~2 rank blocks per byte (gathers), 3 words in / out
+    const double bytes = (double)plen * 65.0 + (double)np * 32.0;
+    if (ix->has_fm2 && !knob(KN_FM_BYTES)) {
+        KLAUNCH("k_loc_seed2", bytes, k_loc_seed2, dim3(blocks(np)), dim3(256), 0, st, fm2_view(ix), d_pats, d_off, np,
+                d_row0, d_width);
+    } else {
+        const FMView f = fm_view(c, ix);
+        KLAUNCH("k_loc_seed", bytes, k_loc_seed, dim3(blocks(np)), dim3(256), 0, st, f, d_pats, d_off, np, d_row0,
+                d_width);
+    }
+    HIPCHECK(hipGetLastError());
 }
 
 }  // namespace bwtmi

@@ -628,6 +628,88 @@ void exclusive_scan(Ctx &c, const T *in, T *out, int64_t n) {
 
 template void exclusive_scan<uint32_t>(Ctx &, const uint32_t *, uint32_t *, int64_t);
 
+// 64-bit exclusive scan (the locate interval widths: one value per piece, a
+// few 10^5 at most in practice): tile-local scans, one workgroup over the tile
+// sums, then the add.  out may alias in: every thread reads its items before
+// it writes them.
+namespace {
+constexpr int kS64Items = 8, kS64Tile = 256 * kS64Items;
+
+// exclusive scan of one value per thread over a 256-thread workgroup; *total = the sum
+__device__ __forceinline__ int64_t block_scan64(int64_t v, int64_t *sh, int64_t *total) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const int64_t add = t >= d ? sh[t - d] : 0;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    const int64_t incl = sh[t];
+    *total = sh[255];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(256) void k_scan64_tile(const int64_t *in, int64_t *out, int64_t n,
+                                                     int64_t *__restrict__ sums) {
+    __shared__ int64_t sh[256];
+    const int64_t base = (int64_t)blockIdx.x * kS64Tile + (int64_t)threadIdx.x * kS64Items;
+    int64_t v[kS64Items], s = 0;
+    for (int q = 0; q < kS64Items; ++q) {
+        v[q] = base + q < n ? in[base + q] : 0;
+        s += v[q];
+    }
+    int64_t total;
+    int64_t run = block_scan64(s, sh, &total);
+    for (int q = 0; q < kS64Items; ++q) {
+        if (base + q < n) out[base + q] = run;
+        run += v[q];
+    }
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// one workgroup: thread t scans the contiguous chunk t of the tile sums
+__global__ __launch_bounds__(256) void k_scan64_sums(int64_t *__restrict__ sums, int64_t ntiles) {
+    __shared__ int64_t sh[256];
+    const int64_t per = (ntiles + 255) / 256;
+    const int64_t a0 = (int64_t)threadIdx.x * per, a = a0 < ntiles ? a0 : ntiles;
+    const int64_t b = a + per < ntiles ? a + per : ntiles;
+    int64_t s = 0;
+    for (int64_t i = a; i < b; ++i) s += sums[i];
+    int64_t total;
+    int64_t run = block_scan64(s, sh, &total);
+    for (int64_t i = a; i < b; ++i) {
+        const int64_t v = sums[i];
+        sums[i] = run;
+        run += v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_scan64_add(int64_t *__restrict__ out, int64_t n,
+                                                    const int64_t *__restrict__ sums) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] += sums[i / kS64Tile];
+}
+}  // namespace
+
+template <>
+void exclusive_scan<int64_t>(Ctx &c, const int64_t *in, int64_t *out, int64_t n) {
+    if (n <= 0) return;
+    const int64_t ntiles = (n + kS64Tile - 1) / kS64Tile;
+    c.slot[S_SCAN_TMP].ensure((size_t)ntiles * 8);
+    int64_t *sums = c.slot[S_SCAN_TMP].as<int64_t>();
+    KLAUNCH("k_scan64_tile", 16.0 * (double)n, k_scan64_tile, dim3((unsigned)ntiles), dim3(256), 0, c.stream, in, out, n,
+            sums);
+    if (ntiles > 1) {
+        KLAUNCH("k_scan64_sums", 16.0 * (double)ntiles, k_scan64_sums, dim3(1), dim3(256), 0, c.stream, sums, ntiles);
+        KLAUNCH("k_scan64_add", 16.0 * (double)n, k_scan64_add, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.stream,
+                out, n, sums);
+    }
+    HIPCHECK(hipGetLastError());
+}
+
 void radix_sort_pairs(Ctx &c, uint64_t *keys, uint64_t *vals, int64_t n, int bit0, int bit1) {
     radix_sort_impl<uint64_t, uint64_t>(c, keys, vals, n, bit0, bit1);
 }

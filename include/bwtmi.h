@@ -186,6 +186,41 @@ int bwtmi_index_tier3(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *reads, co
  * (inclusive interval, or -1,-1). */
 int bwtmi_backward_search_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *pats,
                                 const int64_t *off, int64_t npat, int64_t *sp_ep);
+/* Batched locate with substitutions on one or both strands (not in the
+ * reference: BWTCore.locate_positions, bwt.py:398-410, is the exact,
+ * one-pattern case).  T = the index text (n bytes, sentinel included),
+ * pattern p = pats[off[p] .. off[p+1]), k = max_mismatch in 0..3.
+ *   hit      (pos, strand, d) of a pattern P of m bytes: 0 <= pos, pos + m <= n,
+ *            Q = P on strand '+' (0), revcomp(P) on strand '-' (1),
+ *            d = |{ i : T[pos+i] != Q[i] }| <= k.  The comparison is bytewise
+ *            as in backward_search: no case folding, 'N' is an ordinary byte.
+ *   '$'      is never substituted: a window with a mismatching i where
+ *            T[pos+i] == '$' is no hit (a '$' in the pattern still matches it
+ *            exactly).  So k = 0 yields exactly the sorted SA[sp..ep] of
+ *            backward_search, and no hit hangs over the end of a contig.
+ *   revcomp  MotifUtils.reverse_complement (bwt.py:688) on bytes: A<->T, C<->G, every other
+ *            byte unchanged, reversed.  '-' is searched only with
+ *            BWTMI_LOCATE_BOTH_STRANDS and only when revcomp(P) != P (its hits
+ *            would repeat the '+' ones).
+ *   order    patterns in batch order; a pattern's hits by (pos, strand), '+'
+ *            first; each (pattern, pos, strand) once.  hit_off[npat + 1] are the
+ *            patterns' offsets into pos / mm (= d) / strand; *nhits = hit_off[npat].
+ *   errors   BWTMI_E_ARG, never a silent empty result: an empty pattern,
+ *            m < k + 1, m > 1024, k outside 0..3.  A pattern longer than the
+ *            text, or (k = 0) with bytes the text lacks, is legal: no hits.
+ *   cap      Q is split into k + 1 pieces, piece j = Q[floor(j m / (k+1)),
+ *            floor((j+1) m / (k+1))).  The call's candidate count is the sum,
+ *            over (pattern, searched strand, piece), of the piece's exact
+ *            occurrences in T.  Above max_candidates (<= 0: the default 2^27,
+ *            ~24 bytes of device scratch each) the call fails with
+ *            BWTMI_E_NOMEM and the count in the message; nothing is truncated.
+ *            *candidates (may be NULL) receives the count either way.
+ * The four arrays are malloc'd (never NULL on success; free with bwtmi_free). */
+#define BWTMI_LOCATE_BOTH_STRANDS 1u
+int bwtmi_index_locate_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *pats, const int64_t *off,
+                             int64_t npat, int32_t max_mismatch, uint32_t flags, int64_t max_candidates,
+                             int64_t **hit_off, int64_t **pos, uint8_t **mm, uint8_t **strand, int64_t *nhits,
+                             int64_t *candidates);
 
 /* ------------------------------------------------------------ repeat job
  * Replaces the per-contig worker result handling and the post-processing of
