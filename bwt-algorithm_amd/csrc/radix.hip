@@ -610,13 +610,19 @@ void Ctx::checks_verify(const char *where) {
 
 void exclusive_scan_rows(Ctx &c, const uint32_t *in, uint32_t *out, int64_t n, int rows, int64_t stride) {
     if (n <= 0 || rows <= 0) return;
-    if (rows > kMaxScanRows) fail(BWTMI_E_ARG, "exclusive_scan_rows: %d rows (at most %d)", rows, kMaxScanRows);
     const int64_t ntiles = (n + kTile - 1) / kTile;
-    const LbState lb = lb_prepare(c, ntiles * rows);
-    // 16-byte vectors need aligned bases in every row
-    const int vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0 && (rows == 1 || (stride & 3) == 0) ? 1 : 0;
-    KLAUNCH("k_scan", 2.0 * (double)n * rows * 4.0, k_scan_lb, dim3((unsigned)ntiles, (unsigned)rows), dim3(kBlock), 0,
-            c.stream, in, out, n, ntiles, lb.status, lb.ticket, lb.epoch, vec, stride);
+    // a launch scans at most kMaxScanRows rows (a ticket each); more of them -- the
+    // Occ rows of a text with more than 64 symbols -- take one launch per 64 rows
+    for (int r0 = 0; r0 < rows; r0 += kMaxScanRows) {
+        const int nr = std::min(rows - r0, kMaxScanRows);
+        const uint32_t *pi = in + (int64_t)r0 * stride;
+        uint32_t *po = out + (int64_t)r0 * stride;
+        const LbState lb = lb_prepare(c, ntiles * nr);
+        // 16-byte vectors need aligned bases in every row
+        const int vec = (((uintptr_t)pi | (uintptr_t)po) & 15) == 0 && (nr == 1 || (stride & 3) == 0) ? 1 : 0;
+        KLAUNCH("k_scan", 2.0 * (double)n * nr * 4.0, k_scan_lb, dim3((unsigned)ntiles, (unsigned)nr), dim3(kBlock), 0,
+                c.stream, pi, po, n, ntiles, lb.status, lb.ticket, lb.epoch, vec, stride);
+    }
     HIPCHECK(hipGetLastError());
 }
 

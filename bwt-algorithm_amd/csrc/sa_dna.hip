@@ -1169,7 +1169,9 @@ bool sa_sort(Ctx &c, const uint8_t *t, int64_t n, uint32_t *SA, uint8_t *BWT, in
     std::vector<uint32_t> lstart, lsize, loff;
     ShardedList sl{};   // the first list is plain
     for (int64_t h = 16; G > 0; h *= 2) {
-        if (h >= 2 * n) return false;   // cannot happen ('$' is unique); the general path if it does
+        // only a text of at most 8 bytes that still has a group gets here ("N$":
+        // its first key ties with the zero-padded end's); it takes the general path
+        if (h >= 2 * n) return false;
         // the keys are dead: class lists (5 x (start, size), capacity G each) and
         // the large-group table (3 x <= G) live in their buffer
         c.slot[S_IDX0].ensure((size_t)((2 * kClasses + 3) * G + 16) * 4);

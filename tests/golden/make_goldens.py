@@ -11,6 +11,8 @@ here is product code.  Outputs land in tests/golden/ as small data files:
   rawhits       Tier2LCPFinder.find_long_unit_repeats_strict raw hit lists
   index         BWTCore arrays (SA, BWT, C, Occ, sampled SA, 8-mer hash),
                 Kasai LCP, backward_search / locate / get_kmer_positions
+  index_rates   BWTCore at other sample rates (1 .. n + 1, 2048) and on alphabets
+                of up to 94 symbols: Occ checkpoints, sampled SA, backward_search
   motif         MotifUtils known answers
   library       library finders off the CLI path: short imperfect repeats
                 (FM seeds + Hamming seed-and-extend), LCP plateaus, Tier 1
@@ -407,6 +409,76 @@ def cmd_index(a):
     np.savez_compressed(os.path.join(HERE, "index_arrays.npz"), **arrays)
     with open(os.path.join(HERE, "index_meta.json"), "w") as f:
         json.dump(meta, f)
+
+
+RATE_NS = [1, 2, 15, 16, 17, 127, 128, 129, 300]          # text lengths, sentinel included
+_PRINTABLE = bytes(c for c in range(0x21, 0x7F) if c != ord("$")).decode()   # 93 symbols
+RATE_ALPHABETS = ["ACGT", "ACGTN", "ACGTNRYKM", _PRINTABLE[:15], _PRINTABLE[:16], _PRINTABLE[:17],
+                  _PRINTABLE[:40], _PRINTABLE]
+
+
+def rate_pairs(n):
+    """(sa_sample_rate, occ_sample_rate) of the index_rates grid for a text of n bytes."""
+    return [(1, 1), (7, 16), (32, 48), (33, 100), (1000, 1024), (n, n), (n + 1, n + 1), (2, 2048), (31, 7)]
+
+
+def cmd_index_rates(a):
+    """BWTCore(text, sa_sample_rate, occ_sample_rate) of the reference at rates
+    other than 32 / 128 and on alphabets of up to 94 symbols ->
+    index_rates.json.  Per text (RATE_NS x RATE_ALPHABETS, random symbols with
+    one planted run, + '$'): the text, the byte codes present, a few patterns,
+    and per case a row [sa, occ, occ_len, sampled_len] of rate_pairs with the
+    reference's two lengths.  The numbers themselves -- per case, in this
+    order: the Occ checkpoint row of every byte code of the text (ascending),
+    the sampled SA values (keys 0, sa, 2 sa, ... checked here), (sp, ep) of
+    every pattern -- are one little-endian int16 stream per text (every value
+    is in -1 .. 300), zlib-compressed and base64-encoded ("stream"), which
+    keeps 648 cases under 100 KB.  SA and BWT do not depend on the rates and
+    are not stored.  tests/test_oracle.py reads the file."""
+    import base64
+    import zlib
+    ref = ref_module()
+    out = {}
+    ncases = 0
+    for ai, alpha in enumerate(RATE_ALPHABETS):
+        for n in RATE_NS:
+            rng = np.random.default_rng(1000 * ai + n)
+            body = [alpha[j] for j in rng.integers(0, len(alpha), n - 1)]
+            if n >= 17:
+                p = int(rng.integers(0, n - 9))
+                body[p:p + 8] = [body[p]] * 8
+            body = "".join(body)[:n - 1]
+            text = body + "$"
+            assert len(text) == n and text.isascii()
+            pats = ["", "$", " ", text[:1], text[:1] * 2, text[:2], text[-3:], text[n // 2:n // 2 + 3],
+                    body[-1:] + body[:1]]
+            pats = list(dict.fromkeys(pats))
+            stream, cases, codes = [], [], None
+            for sa, occ in rate_pairs(n):
+                core = ref.BWTCore(text, sa, occ)
+                cp = {int(c): np.asarray(v).tolist() for c, v in core.occ_checkpoints.items()}
+                if codes is None:
+                    codes = sorted(cp)
+                assert sorted(cp) == codes == sorted(set(text.encode()))
+                lens = {len(v) for v in cp.values()}
+                assert len(lens) == 1
+                for c in codes:
+                    stream += cp[c]
+                samp = {int(k): int(v) for k, v in core.sampled_sa.items()}
+                assert list(samp) == list(range(0, n, sa)), (n, sa)
+                stream += list(samp.values())
+                for p in pats:
+                    stream += [int(x) for x in core.backward_search(p)]
+                cases.append([sa, occ, lens.pop(), len(samp)])
+                ncases += 1
+            assert min(stream) >= -1 and max(stream) <= 300
+            blob = zlib.compress(np.asarray(stream, dtype="<i2").tobytes(), 9)
+            out[f"a{ai}_n{n}"] = dict(text=text, patterns=pats, cases=cases, values=len(stream),
+                                      stream=base64.b64encode(blob).decode())
+    path = os.path.join(HERE, "index_rates.json")
+    with open(path, "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+    print(ncases, "cases", os.path.getsize(path), "bytes")
 
 
 def cmd_motif(a):
@@ -826,6 +898,7 @@ def main():
     p = sp.add_parser("fixtures"); p.add_argument("--check-hybrid", action="store_true")
     sp.add_parser("rawhits")
     sp.add_parser("index")
+    sp.add_parser("index_rates")
     sp.add_parser("motif")
     sp.add_parser("library")
     sp.add_parser("tier3")
@@ -847,7 +920,7 @@ def main():
     p.add_argument("--keep-rows", type=int, default=0)
     p.add_argument("--save-out", action="store_true")
     a = ap.parse_args()
-    dict(fixtures=cmd_fixtures, rawhits=cmd_rawhits, index=cmd_index, motif=cmd_motif,
+    dict(fixtures=cmd_fixtures, rawhits=cmd_rawhits, index=cmd_index, index_rates=cmd_index_rates, motif=cmd_motif,
          hybrid=cmd_hybrid, homopolymer=cmd_homopolymer, library=cmd_library, tier3=cmd_tier3, simple=cmd_simple, edge=cmd_edge)[a.cmd](a)
 
 

@@ -128,15 +128,12 @@ def test_exact_equals_locate_positions(texts, cfg):
 
 
 # ------------------------------------------------------------------ 2. parity
-@pytest.mark.parametrize("both", [False, True])
-@pytest.mark.parametrize("k", [0, 1, 2, 3])
-@pytest.mark.parametrize("name", ["acgt", "gaps"])
-def test_brute_force_parity(texts, name, k, both):
-    text, core = texts[name]
-    T = np.frombuffer(text, dtype=np.uint8)
-    rng = np.random.default_rng(1000 + 10 * k + int(both))
+def _parity_patterns(rng, T, k, lengths=(2, 3, 4, 8, 9, 16, 17, 33, 64, 200)):
+    """Pieces of the `texts` fixture's text (its planted copies, the N run, the
+    end, random places) with 0 .. k + 1 substitutions, some reverse-complemented,
+    and one random pattern per length."""
     pats = []
-    for m in (2, 3, 4, 8, 9, 16, 17, 33, 64, 200):
+    for m in lengths:
         if m < k + 1:
             continue
         starts = [100, 1500 + (200 - m) // 2, 2300, 395, 2990 - m // 2] + rng.integers(0, T.size - 1 - m, 3).tolist()
@@ -147,10 +144,39 @@ def test_brute_force_parity(texts, name, k, both):
             if j % 3 == 0:
                 pats.append(revcomp(seg.tobytes()))
         pats.append(_random_dna(rng, m).tobytes())
+    return pats
+
+
+@pytest.mark.parametrize("both", [False, True])
+@pytest.mark.parametrize("k", [0, 1, 2, 3])
+@pytest.mark.parametrize("name", ["acgt", "gaps"])
+def test_brute_force_parity(texts, name, k, both):
+    text, core = texts[name]
+    T = np.frombuffer(text, dtype=np.uint8)
+    rng = np.random.default_rng(1000 + 10 * k + int(both))
+    pats = _parity_patterns(rng, T, k)
     res = check_against_oracle(core, text, pats, k, both)
     assert res.positions.size > len(pats) // 2      # the cases are not vacuous
     if k and both:
         assert res.mismatches.max() == k and res.strand.any()
+
+
+@pytest.mark.parametrize("sa,occ", [(1, 1), (7, 16), (33, 100), (1000, 2048)])
+def test_sample_rates_do_not_change_hits(texts, sa, occ):
+    """The hits do not depend on the index's sample rates: the gap text (seed
+    search over the byte Occ, d_rank with a block of occ bytes) and the ACGT
+    text under BWTMI_FM_BYTES=1, rebuilt at other rates, against the brute
+    force, which knows no rates."""
+    from bwtmi import BWTCore, _lib
+    rng = np.random.default_rng(4000 + sa)
+    for name, fm_bytes in (("gaps", 0), ("acgt", 1)):
+        text = texts[name][0]
+        pats = _parity_patterns(rng, np.frombuffer(text, dtype=np.uint8), 1, lengths=(4, 33))
+        assert 20 <= len(pats) <= 30
+        core = BWTCore(text, sa, occ, build_kmer=False)
+        with _lib.knobs(FM_BYTES=fm_bytes):
+            res = check_against_oracle(core, text, pats, 1, True)
+        assert res.positions.size > len(pats) // 2 and res.strand.any()
 
 
 # ------------------------------------------------------------------ 3. dedup

@@ -85,6 +85,63 @@ def test_index_arrays_match_reference(golden_dir):
             assert list(ix.backward_search(p.encode())) == iv, (key, p)
 
 
+def _index_rate_cases(golden_dir):
+    """(key, text, patterns, sa, occ, occ_len, sampled_len, numbers) per case of
+    index_rates.json; `numbers` is the case's slice of the text's int16 stream
+    (make_goldens.py cmd_index_rates states the order)."""
+    import base64
+    import zlib
+    for key, t in _load(golden_dir, "index_rates.json").items():
+        text = t["text"].encode()
+        codes = sorted(set(text))
+        vals = np.frombuffer(zlib.decompress(base64.b64decode(t["stream"])), dtype="<i2").astype(np.int64)
+        assert vals.size == t["values"], key
+        at = 0
+        for sa, occ, occ_len, sampled_len in t["cases"]:
+            k = len(codes) * occ_len + sampled_len + 2 * len(t["patterns"])
+            yield key, text, t["patterns"], sa, occ, occ_len, sampled_len, vals[at:at + k]
+            at += k
+        assert at == vals.size, key
+
+
+def test_index_rates_match_reference(golden_dir):
+    """oracle.Index(text, sa, occ) at sample rates from 1 to n + 1 and 2048 and
+    on alphabets of 4 to 93 symbols + '$' (bytes below '$', lower case): the
+    reference's Occ checkpoint rows, sampled SA and backward-search intervals."""
+    ncases = 0
+    for key, text, pats, sa, occ, occ_len, sampled_len, vals in _index_rate_cases(golden_dir):
+        ix = oracle.Index(text, sa, occ)
+        codes = sorted(set(text))
+        assert ix.alphabet() == codes, key
+        assert ix.occ.shape[1] == occ_len, (key, sa, occ)
+        rows = vals[:len(codes) * occ_len].reshape(len(codes), occ_len)
+        for c, row in zip(codes, rows):
+            assert ix.occ[c].tolist() == row.tolist(), (key, sa, occ, c)
+        samp = vals[len(codes) * occ_len:][:sampled_len]
+        assert ix.sampled_sa == {i * sa: int(v) for i, v in enumerate(samp)}, (key, sa, occ)
+        iv = vals[len(codes) * occ_len + sampled_len:].reshape(len(pats), 2)
+        for p, want in zip(pats, iv.tolist()):
+            assert list(ix.backward_search(p.encode())) == want, (key, sa, occ, p)
+        ncases += 1
+    assert ncases == 648
+
+
+def test_occ_checkpoints_plain_restatement(golden_dir):
+    """The same grid against the definition: occ[c][j] counts c in
+    bwt[:min(j * occ, n)], and a row has 1 + n // occ + (n % occ != 0) entries."""
+    for key, text, _, sa, occ, occ_len, _, _ in _index_rate_cases(golden_dir):
+        ix = oracle.Index(text, sa, occ)
+        n = len(text)
+        want_len = 1 + n // occ + (n % occ != 0)
+        assert occ_len == want_len and ix.occ.shape[1] == want_len, (key, occ)
+        ends = np.minimum(np.arange(want_len, dtype=np.int64) * occ, n)
+        for c in sorted(set(text)):
+            prefix = np.concatenate([[0], np.cumsum(ix.bwt == c)])
+            assert (ix.occ[c] == prefix[ends]).all(), (key, occ, c)
+        for c in set(range(256)) - set(text):
+            assert not ix.occ[c].any(), (key, occ, c)
+
+
 def test_threaded_suffix_array_equals_serial(golden_dir):
     """The baseline's threaded prefix doubling (chunk sorts + co-rank merges +
     chunked re-rank) returns the reference's suffix array: on every golden
