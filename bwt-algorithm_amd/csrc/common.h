@@ -42,6 +42,44 @@ using HitVec = std::vector<bwtmi_hit, NoInit<bwtmi_hit>>;
 // lbits), lbits = the bits of the longest span -- when len and prim fit the
 // high half (32 B per hit on the device, 8 B over PCIe), else as two words
 // {start, len | prim << 32}.
+// Each record also carries the hit's CUT bit (fold_cut below): bit 63 of the
+// one word -- used only when lbits + pbits + 1 <= 32, pbits = the bits of the
+// longest primitive motif -- or bit 63 of the second word.
+//
+// ---- how far a record built from a strict hit can ever end (nested.hip's
+// drop and the fold cuts of post.cpp share this one definition).
+// A merge (bwt.py:3222-3289) needs same canonical motifs (equal motif lengths
+// M) within a gap of M + 1.  A record built from the hit (s, e, m) and hits
+// after it ends at most at max(e, s + m min_copies) + 2 ext(m): the
+// recompute's walk limit (motif.cpp / post.cpp), once for the merge and once
+// for the refine; ext(m) = max(3m, 4 min(10, m/2 or 1)).
+// unit1_maximal: the hit comes from the device scan, where a unit-1 hit is a
+// maximal run of its base.  A one-base record is the closed form -- the run of
+// its first base through its start, capped at the walk limit -- so a record
+// built from such hits ends at its first hit's end and has no mismatches to
+// refine: its bound is its end.  Hits handed in through bwtmi_job_add_hits
+// need not be maximal runs and take the general formula.
+#if defined(__HIPCC__)
+#define BWTMI_HD __host__ __device__
+#else
+#define BWTMI_HD
+#endif
+BWTMI_HD inline int64_t screen_reach(int64_t s, int64_t e, int64_t m, int32_t mc, bool unit1_maximal) {
+    if (m == 1 && unit1_maximal) return e;
+    const int64_t mi = m >= 4 ? (m / 2 < 10 ? m / 2 : 10) : 1;
+    const int64_t ext = 3 * m > 4 * mi ? 3 * m : 4 * mi;
+    const int64_t w = s + m * (int64_t)mc;
+    return (e > w ? e : w) + 2 * ext;
+}
+// Hit k of a (start, end) sorted hit list is a CUT when no record built from
+// the hits before it can come within merging distance of it:
+//   S[k] - max_{j < k} reach(j) > max(1, M[k]) + 1        (k == 0: always)
+// reach_before = that maximum (INT64_MIN: none).  post.cpp (fold_cuts) states
+// what follows from it.
+BWTMI_HD inline bool fold_cut(int64_t s, int64_t m, int64_t reach_before) {
+    return reach_before == INT64_MIN || s - reach_before > (m > 1 ? m : 1) + 1;
+}
+
 // a device download still landing in host memory (nested.hip): wait(k) returns
 // once hits [0, k) are there; the destructor waits for all of it
 struct Landing {
@@ -52,6 +90,7 @@ struct Landing {
 struct ScreenedVec {
     std::vector<uint64_t, NoInit<uint64_t>> w;
     int32_t lbits = -1;   // one word per hit when >= 0
+    bool dropped = false; // the screen dropped kept hits (their reach still counts in the cut bits)
     // the download into w, when it is still in flight: declared after w, so it
     // is destroyed (and waited for) before w is freed
     std::shared_ptr<Landing> landing;
@@ -65,25 +104,29 @@ struct ScreenedVec {
         landing.reset();
         w.clear();
         lbits = -1;
+        dropped = false;
     }
     void swap(ScreenedVec &o) noexcept {
         w.swap(o.w);
         std::swap(lbits, o.lbits);
+        std::swap(dropped, o.dropped);
         landing.swap(o.landing);
     }
-    // hit k: start, length, primitive motif length
-    void get(int64_t k, int64_t &start, int64_t &len, int64_t &prim) const {
+    // hit k: start, length, primitive motif length; returns its cut bit
+    bool get(int64_t k, int64_t &start, int64_t &len, int64_t &prim) const {
+        constexpr uint64_t kCut = uint64_t(1) << 63;
         if (lbits >= 0) {
             const uint64_t x = w[(size_t)k];
             start = (int64_t)(uint32_t)x;
             len = (int64_t)((x >> 32) & ((uint64_t(1) << lbits) - 1));
-            prim = (int64_t)(x >> (32 + lbits));
-        } else {
-            start = (int64_t)w[2 * (size_t)k];
-            const uint64_t y = w[2 * (size_t)k + 1];
-            len = (int64_t)(uint32_t)y;
-            prim = (int64_t)(y >> 32);
+            prim = (int64_t)((x & ~kCut) >> (32 + lbits));
+            return (x & kCut) != 0;
         }
+        start = (int64_t)w[2 * (size_t)k];
+        const uint64_t y = w[2 * (size_t)k + 1];
+        len = (int64_t)(uint32_t)y;
+        prim = (int64_t)((y & ~kCut) >> 32);
+        return (y & kCut) != 0;
     }
 };
 
@@ -469,7 +512,7 @@ enum Knob {
     KN_RUNS_DENSE, KN_RUNS_UNTILED, KN_SA_SMALL, KN_SEG_LEVELS, KN_SCREEN_WIDE, KN_FM_BYTES, KN_LS_CAP,
     KN_HOST_SCREEN, KN_NO_PLAIN, KN_INDEX_LANES, KN_SCAN_LANES, KN_NO_AVX512, KN_POOL_SPIN_US,
     KN_UNIT_GROUP_THREADS, KN_STATS, KN_NUMA_BIND, KN_NUMA_SMT, KN_FAIL_MERGE_CHUNK, KN_HIST_S, KN_DEVICE_CHECKS,
-    KN_SCREEN_DROP, KN_COUNT
+    KN_SCREEN_DROP, KN_FOLD_CUTS, KN_FOLD_CHUNK, KN_COUNT
 };
 // a roctx range for the lifetime of the object (trace.cpp); names "bwtmi:<stage>"
 struct StageRange {

@@ -355,10 +355,11 @@ void strict_scan_mm_device(Ctx &c, const uint8_t *d_text, int64_t n, int32_t min
 // ----- nested suppression / sort / dedup of one contig's strict hits (nested.hip)
 // maxlen: the hits' longest span, when the caller knows it (the strict scan's
 // compaction reduces it and reads it with the hit count); -1: reduced here
-// drop_min_copies > 0: also drop the kept hits the post-processing would only
-// carry to its final filter (k_drop_flags; the job's min_copies)
+// min_copies: the job's (the reach of a hit, screen_reach in common.h, and with
+// it every downloaded hit's cut bit).  drop: also drop the kept hits the
+// post-processing would only carry to its final filter (k_drop_flags)
 void screen_hits_device(Ctx &c, const bwtmi_hit *d_hits, int64_t n, int64_t text_len, int32_t lmax,
-                        ScreenedVec &out, int64_t maxlen = -1, int32_t drop_min_copies = 0);
+                        ScreenedVec &out, int64_t maxlen, int32_t min_copies, bool drop);
 
 // ----- suffix array + BWT of ACGT* '$' texts (sa_dna.hip)
 bool sa_dna_eligible(uint8_t last, int64_t n, const int64_t *totals);

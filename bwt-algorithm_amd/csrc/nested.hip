@@ -471,13 +471,8 @@ __global__ __launch_bounds__(kB) void k_level_wave(const uint32_t *__restrict__ 
 // the output unchanged when it is dropped here:
 //   merge (bwt.py:3222-3289): a merge needs same canonical motifs (equal
 //     motif lengths M) within a gap of M + 1.  A record built from records
-//     before the hit ends at most at max(e, s + M min_copies) + 2 ext(M) of
-//     one of them (the recompute's walk limit, motif.cpp / post.cpp, once for
-//     the merge and once for the refine; ext(M) = max(3M, 4 min(10, M/2 or 1))),
-//     A one-base record is the closed form: the run of its first base through
-//     its start, capped at the walk limit -- a unit-1 strict hit is a maximal
-//     run, so a record built from such hits ends at its first hit's end, and
-//     it has no mismatches to refine: its bound is its end.
+//     before the hit ends at most at screen_reach() of one of them (common.h;
+//     the hits here come from the device scan, so a unit-1 hit is a maximal run).
 //     So with R = max over the earlier kept hits of that bound,
 //     start - R > M_hit + 1 keeps every earlier record out of reach; with
 //     next.start - end > max(M_hit, M_next) + 1 the hit merges with nothing
@@ -489,13 +484,11 @@ __global__ __launch_bounds__(kB) void k_level_wave(const uint32_t *__restrict__ 
 // (non-kept entries contribute nothing; k_final_flags writes it); the next
 // kept hit is found by a short probe forward (kept hits are dense: a probe
 // that finds none within kDropProbe ranks keeps the hit).
+// The same R gives every downloaded hit its cut bit (fold_cut, common.h;
+// k_final_compact), whether or not the drop is on: R covers every kept hit
+// before the drop, a superset of the hits the host folds, so the bound holds
+// for them too.
 constexpr int kDropProbe = 64;
-__device__ __forceinline__ int64_t screen_reach(int64_t s, int64_t e, int64_t m, int32_t mc) {
-    if (m == 1) return e;
-    const int64_t mi = m >= 4 ? min<int64_t>(10, m / 2) : 1;
-    const int64_t ext = max<int64_t>(3 * m, 4 * mi);
-    return max(e, s + m * (int64_t)mc) + 2 * ext;
-}
 // out[k] = flag[k], cleared for a droppable kept hit (R: inclusive prefix max;
 // flag is read only, so every probe sees the kept set before the drop)
 __global__ void k_drop_flags(const int64_t *__restrict__ S, const int64_t *__restrict__ E,
@@ -519,32 +512,35 @@ __global__ void k_drop_flags(const int64_t *__restrict__ S, const int64_t *__res
     out[k] = 0u;
 }
 
-// R (drop_mc > 0): the reach of each kept hit, INT64_MIN elsewhere (k_drop_flags)
+// R: the reach of each kept hit, INT64_MIN elsewhere (k_drop_flags, k_final_compact)
 __global__ void k_final_flags(const int64_t *__restrict__ S, const int64_t *__restrict__ E,
                               const int32_t *__restrict__ M, const uint8_t *__restrict__ kept, int64_t n,
-                              uint32_t *__restrict__ flag, int32_t drop_mc, int64_t *__restrict__ R) {
+                              uint32_t *__restrict__ flag, int32_t mc, int64_t *__restrict__ R) {
     const int64_t k = (int64_t)blockIdx.x * kB + threadIdx.x;
     if (k >= n) return;
     bool f = kept[k] != 0;
     if (f && k > 0 && S[k - 1] == S[k] && E[k - 1] == E[k] && M[k - 1] == M[k]) f = false;
     flag[k] = f ? 1u : 0u;
-    if (drop_mc > 0) R[k] = f ? screen_reach(S[k], E[k], max<int64_t>(1, M[k]), drop_mc) : INT64_MIN;
+    R[k] = f ? screen_reach(S[k], E[k], max<int64_t>(1, M[k]), mc, true) : INT64_MIN;
 }
 
 // kept hits in screen order, one 64-bit word each (lbits >= 0: start | len << 32
-// | prim << (32 + lbits)) or two ({start, len | prim << 32}); common.h ScreenedVec
+// | prim << (32 + lbits)) or two ({start, len | prim << 32}), the hit's cut bit
+// (R: the inclusive prefix max of the reaches) in bit 63 of the last word;
+// common.h ScreenedVec
 __global__ void k_final_compact(const bwtmi_hit *__restrict__ H, const uint32_t *__restrict__ vpos,
-                                const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, int64_t n,
-                                int lbits, uint64_t *__restrict__ out) {
+                                const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                                const int64_t *__restrict__ R, int64_t n, int lbits, uint64_t *__restrict__ out) {
     const int64_t k = (int64_t)blockIdx.x * kB + threadIdx.x;
     if (k >= n || !flag[k]) return;
     const bwtmi_hit h = H[vpos[k]];
     const uint64_t len = (uint64_t)(h.end - h.start), prim = (uint64_t)(uint32_t)h.prim_len;
+    const uint64_t cut = fold_cut(h.start, h.prim_len, k > 0 ? R[k - 1] : INT64_MIN) ? uint64_t(1) << 63 : 0;
     if (lbits >= 0) {
-        out[pos[k]] = (uint64_t)(uint32_t)h.start | len << 32 | prim << (32 + lbits);
+        out[pos[k]] = (uint64_t)(uint32_t)h.start | len << 32 | prim << (32 + lbits) | cut;
     } else {
         out[2 * (int64_t)pos[k]] = (uint64_t)h.start;
-        out[2 * (int64_t)pos[k] + 1] = (len & 0xFFFFFFFFull) | prim << 32;
+        out[2 * (int64_t)pos[k] + 1] = (len & 0xFFFFFFFFull) | prim << 32 | cut;
     }
 }
 
@@ -583,7 +579,7 @@ static void screen_levels(Ctx &c, const bwtmi_hit *d_hits, int64_t n, int32_t lm
 }
 
 void screen_hits_device(Ctx &c, const bwtmi_hit *d_hits, int64_t n, int64_t text_len, int32_t lmax,
-                        ScreenedVec &out, int64_t maxlen_known, int32_t drop_min_copies) {
+                        ScreenedVec &out, int64_t maxlen_known, int32_t min_copies, bool drop_unit) {
     out.clear();
     if (n <= 0) return;
     if (n >= (int64_t)UINT32_MAX) fail(BWTMI_E_ARG, "too many strict hits for one contig (%lld)", (long long)n);
@@ -653,33 +649,35 @@ void screen_hits_device(Ctx &c, const bwtmi_hit *d_hits, int64_t n, int64_t text
     // every level, segment by segment, in one launch (BWTMI_SEG_LEVELS=0: per-level launches)
     const bool seg_levels = knob(KN_SEG_LEVELS) != 0;
     unsigned int *d_ovf = reinterpret_cast<unsigned int *>(d_max);   // [0] fallback flag, [1] overflow windows
-    // one word per kept hit when the start fits the low half and the longest span
-    // and the longest primitive motif fit the high half (BWTMI_SCREEN_WIDE=1:
-    // always two)
+    // one word per kept hit when the start fits the low half and the longest span,
+    // the longest primitive motif and the cut bit fit the high half
+    // (BWTMI_SCREEN_WIDE=1: always two)
     const bool wide = knob(KN_SCREEN_WIDE) != 0;
     const int lbits = lb;   // bits of the longest span (hit lengths are <= maxlen)
     const int pbits = std::max(1, bits_for((uint64_t)lmax));
-    out.lbits = !wide && lbits + pbits <= 32 && bits_for((uint64_t)text_len) <= 32 ? lbits : -1;
+    out.lbits = !wide && lbits + pbits + 1 <= 32 && bits_for((uint64_t)text_len) <= 32 ? lbits : -1;
     // the kept flags -> their order -> the packed records, and the kept count
     // with the screen's overflow flag (mb[1]) in the same stream wait
     // records only the final filter would see are dropped here (k_drop_flags;
     // BWTMI_SCREEN_DROP=0 keeps them): at C3 most kept hits are short runs
-    const bool drop = drop_min_copies > 0 && knob(KN_SCREEN_DROP) != 0;
+    // the reaches R and their prefix max run either way: the cut bits need them
+    const bool drop = drop_unit && knob(KN_SCREEN_DROP) != 0;
+    out.dropped = drop;
     if (drop) c.slot[S_IDX7].ensure((size_t)(n + 1) * 4);
     auto final_pass = [&] {
-        int64_t *R = drop ? c.slot[S_CAND_K].as<int64_t>() : nullptr;   // (the sorted keys are spent)
+        int64_t *R = c.slot[S_CAND_K].as<int64_t>();   // (the sorted keys are spent)
         KLAUNCH("k_final_flags", 0.0, k_final_flags, dim3(blocks(n)), dim3(kB), 0, st, S, E, M, kept, n, flag,
-                drop ? drop_min_copies : 0, R);
+                min_copies, R);
+        prefix_max(c, R, R, n, c.slot[S_IDX5].as<int64_t>());
         uint32_t *fl = flag;   // the flags the compaction takes
         if (drop) {
             fl = c.slot[S_IDX7].as<uint32_t>();
-            prefix_max(c, R, R, n, c.slot[S_IDX5].as<int64_t>());
             KLAUNCH("k_drop_flags", 0.0, k_drop_flags, dim3(blocks(n)), dim3(kB), 0, st, S, E, M, flag, R, n,
-                    drop_min_copies, fl);
+                    min_copies, fl);
         }
         HIPCHECK(hipMemsetAsync(fl + n, 0, 4, st));
         exclusive_scan<uint32_t>(c, fl, pos, n + 1);
-        KLAUNCH("k_final_compact", 0.0, k_final_compact, dim3(blocks(n)), dim3(kB), 0, st, d_hits, vpos, fl, pos, n,
+        KLAUNCH("k_final_compact", 0.0, k_final_compact, dim3(blocks(n)), dim3(kB), 0, st, d_hits, vpos, fl, pos, R, n,
                 out.lbits, dout);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipMemcpyAsync(reinterpret_cast<uint32_t *>(mb), pos + n, 4, hipMemcpyDeviceToHost, st));

@@ -1557,12 +1557,331 @@ void materialize(const UnitCtx &u, const Item &it, int64_t shift, Rec &r) {   //
     }
 }
 
+// ------------------------------------------------- one pass over cut segments
+// For a unit of one contig whose input records are all strict hits, in
+// (start, end) order, hit k is a CUT (fold_cut, common.h) when
+//   S[k] - max_{j < k} reach(j) > max(1, M[k]) + 1,
+// reach(j) (screen_reach) being how far a record built from hit j and hits
+// after it is expected to end: by a merge, a chain of merges, or the refine of
+// such a record.  Where every record from before hit k does end at most at
+// R = max reach(j),
+//   * the fold restarts.  The record the fold holds when hit k arrives was
+//     built from earlier hits; the merge test asks for a gap of at most
+//     min(mlen) + 1, and min(mlen) + 1 <= M[k] + 1 because hit k's own motif
+//     length is one of the two: the test fails, the record is emitted and hit k
+//     becomes the current record, fresh.  Every earlier record has been emitted
+//     by then, and the fold only ever looks at its current record: what it does
+//     from k on does not depend on anything before k;
+//   * the collapse restarts.  It compares a record with the last one it kept,
+//     and collapsing needs an overlap.  Every record from before the cut ends
+//     (refined or not) at most at R < S[k], every record from k on starts at
+//     S[k] or later (a merged record starts where its first hit did);
+//   * the (start, end) order holds across the cut: a record ends after it
+//     starts, so every start before the cut is < S[k] <= every start after it,
+//     and the equal-start runs that the refine can put out of order lie inside
+//     segments;
+//   * hits that the device screen dropped only loosen the bound.  Its R runs
+//     over every kept hit before the drop, a superset of the hits folded here,
+//     so R is at least the maximum over the hits that are left.
+// So the segments between consecutive cuts are independent from the fold to
+// the final filter (bwt.py:3222-3289, 3291-3314, 3499-3513, 3940-3944), and a
+// task runs all of it on one segment at a time, while its records are in
+// cache, and keeps only the survivors.  Nothing is speculated.
+//
+// reach() is the recompute's walk limit, and the walk's last copy starts before
+// that limit but may end up to m + max_indel - 1 past it (motif.cpp); a chain of
+// merges can also carry a walk on from where the last one stopped.  So a bit is
+// taken as a hint, and a cut is USED only once it is verified on the records
+// themselves: the fold runs its ordinary merge test at hit k, and the segment
+// is closed there only if that test failed and every record of the segment,
+// after its refine, ends at most at S[k] - max(1, M[k]) - 2 -- the three points
+// above with the real ends in place of R.  An unverified bit is an ordinary
+// hit.  A task that finds the bit at its end unverified folds on to the next
+// verified cut; the tasks it ran through are folded again from there, serially
+// (reconcile below; rare: on a 200 kbp contig with 2 % substitutions one bit
+// in ~8000 fails, and only one at a task's edge costs anything).
+struct CutSrc {
+    const ScreenedVec *sh = nullptr;   // device-screened hits, or
+    const ItemVec *recs = nullptr;     // host-screened records and their bits
+    const uint8_t *cut = nullptr;
+    int32_t chrom = 0;
+    int64_t n = 0;
+    void wait(int64_t k) const {   // records [0, k) readable
+        if (sh) sh->wait(std::min(k, n));
+    }
+    bool get(int64_t k, Item &it) const {   // record k; true: a cut
+        if (sh) {
+            int64_t s0, len, prim;
+            const bool c = sh->get(k, s0, len, prim);
+            it = Item{s0, s0 + len, nullptr, chrom, (int32_t)prim};
+            return c || k == 0;   // (the screen may have dropped the hits before the first one)
+        }
+        it = (*recs)[(size_t)k];
+        return cut[k] != 0;
+    }
+};
+
+// the cut bits of n strict hits in (start, end) order, at(k, s, e, m): the
+// largest reach per chunk in parallel, a prefix over the chunks, a sequential
+// prefix inside each chunk (the pattern of the collapse's `sb`)
+template <class At>
+std::vector<uint8_t> host_cuts(int64_t n, int64_t min_copies, bool unit1_maximal, int nt, At &&at) {
+    std::vector<uint8_t> cut((size_t)n);
+    const int32_t mc = (int32_t)std::max<int64_t>(1, std::min<int64_t>(min_copies, INT32_MAX));
+    const int C = n > 8192 ? 4 * std::max(1, nt) : 1;
+    std::vector<int64_t> cmax((size_t)C, INT64_MIN), pre((size_t)C, INT64_MIN);
+    auto reach = [&](int64_t k) {
+        int64_t s, e, m;
+        at(k, s, e, m);
+        return screen_reach(s, e, std::max<int64_t>(1, m), mc, unit1_maximal);
+    };
+    if (C > 1)
+        parallel_items(C, nt, [&](int64_t t, int) {
+            int64_t r = INT64_MIN;
+            for (int64_t k = n * t / C; k < n * (t + 1) / C; ++k) r = std::max(r, reach(k));
+            cmax[(size_t)t] = r;
+        });
+    for (int t = 1; t < C; ++t) pre[(size_t)t] = std::max(pre[(size_t)t - 1], cmax[(size_t)t - 1]);
+    parallel_items(C, nt, [&](int64_t t, int) {
+        int64_t r = pre[(size_t)t];
+        for (int64_t k = n * t / C; k < n * (t + 1) / C; ++k) {
+            int64_t s, e, m;
+            at(k, s, e, m);
+            cut[(size_t)k] = fold_cut(s, m, r);
+            r = std::max(r, reach(k));
+        }
+    });
+    return cut;
+}
+
+// BWTMI_DEVICE_CHECKS=1: the device's cut bits against the host's.  Without
+// the drop they are equal; with it the device's bound also covers the dropped
+// hits, so it may only be the stricter one (a device cut is a host cut).
+void check_device_cuts(const UnitCtx &u, const ScreenedVec &sh, int nt) {
+    const int64_t n = sh.size();
+    sh.wait(n);
+    const std::vector<uint8_t> hc = host_cuts(n, u.min_copies, true, nt, [&](int64_t k, int64_t &s, int64_t &e, int64_t &m) {
+        int64_t len;
+        (void)sh.get(k, s, len, m);
+        e = s + len;
+    });
+    for (int64_t k = 0; k < n; ++k) {
+        int64_t s, len, m;
+        const bool d = sh.get(k, s, len, m);
+        if (sh.dropped ? d && !hc[(size_t)k] : d != (hc[(size_t)k] != 0))
+            fail(BWTMI_E_STATE, "cut bit of screened hit %lld (start %lld, unit %lld): device %d, host %d", (long long)k,
+                 (long long)s, (long long)m, (int)d, (int)hc[(size_t)k]);
+    }
+}
+
+// The fused pass.  Tasks are nominal chunks of records (BWTMI_FOLD_CHUNK
+// records each; 0: the merge fold's rule), claimed in ascending order; task k
+// owns the records from the first cut at or after its nominal start up to the
+// first cut at or after its nominal end (none in its range: nothing), and
+// waits for the download of those records only.
+void fold_cuts(const UnitCtx &u, Pools &pools, const CutSrc &src, int nt, int64_t shift, RecVec &out, double *ms) {
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    const int64_t n = src.n;
+    if (n == 0) return;
+    const int64_t chunk = std::max<int64_t>(0, knob(KN_FOLD_CHUNK));
+    const int64_t K = chunk > 0 ? (n + chunk - 1) / chunk : std::max<int64_t>(1, std::min<int64_t>((int64_t)nt * 8, n / 2048 + 1));
+    auto nom = [&](int64_t k) { return chunk > 0 ? std::min(n, k * chunk) : n * k / K; };
+    // test hook: BWTMI_FAIL_MERGE_CHUNK=k throws inside task k (-2: the last task)
+    const int64_t inj_k = knob(KN_FAIL_MERGE_CHUNK);
+    const int64_t inj = inj_k == -1 ? -1 : inj_k < 0 ? K - 1 : inj_k;
+    const double mcd = (double)u.job->params.min_copies;
+    // per task: the records that pass the final filter (slot K: a tail the reconcile folds)
+    std::vector<std::vector<Item>> surv((size_t)K + 1);
+    std::vector<int64_t> first((size_t)K, -1), stop((size_t)K, -1);   // the range a task folded: [first, stop)
+    std::vector<double> cms(stats_on() ? (size_t)K : 0);
+    std::atomic<int64_t> n_cuts{0}, n_unverified{0}, n_folded{0}, n_collapsed{0};
+    auto lt = [](const Item &a, const Item &b) { return a.start != b.start ? a.start < b.start : a.end < b.end; };
+    // the fold from record i (a verified cut, or 0) to the first verified cut at
+    // or after ne (returned; n: the end), survivors appended to sv
+    auto fold_range = [&](int64_t i, int64_t ne, int w, std::vector<Item> &sv) -> int64_t {
+        std::vector<Item> seg;   // the fold's output since the last verified cut
+        size_t refined = 0;      // seg[0, refined) have been through refine
+        int64_t mx = INT64_MIN;  // the largest end in seg, before or after refine
+        int64_t cuts = 1, unverified = 0, folded = 0, collapsed = 0, waited = 0;
+        auto refine_seg = [&] {
+            for (; refined < seg.size(); ++refined) {
+                Item &it = seg[refined];
+                mx = std::max(mx, it.end);
+                if (it.imperfect()) {
+                    refine_one(u, pools, w, it);
+                    mx = std::max(mx, it.end);
+                }
+            }
+        };
+        // order, collapse and filter the (refined) segment
+        auto close_seg = [&] {
+            // the fold's output is ordered by start and refine only moves ends:
+            // equal-start runs go by end (any other disorder: the same stable sort)
+            if (!std::is_sorted(seg.begin(), seg.end(), lt)) std::stable_sort(seg.begin(), seg.end(), lt);
+            folded += (int64_t)seg.size();
+            auto emit = [&](const Item &x) {
+                ++collapsed;
+                if (copies_of(x) >= mcd && x.end - x.start >= 6) sv.push_back(x);
+            };
+            Item last = seg[0];   // the slot takes the preferred record
+            for (size_t q = 1; q < seg.size(); ++q) {
+                if (should_collapse(u, last, seg[q])) {
+                    if (!prefer_first(u, last, seg[q])) last = seg[q];
+                } else {
+                    emit(last);
+                    last = seg[q];
+                }
+            }
+            emit(last);
+            seg.clear();
+            refined = 0;
+            mx = INT64_MIN;
+        };
+        Item cur, r, mg;
+        src.wait(waited = std::min(n, std::max(ne, i + 1)));
+        (void)src.get(i, cur);
+        Canon cb[2];   // canonical forms of cur and of the next record; roles swap by index
+        int ci_cur = 0;
+        int64_t j = i + 1;
+        for (; j < n; ++j) {
+            if (j >= waited) src.wait(waited = std::min(n, j + 256));   // past the nominal end, up to the next cut
+            const bool bit = src.get(j, r);
+            Canon &cc = cb[ci_cur], &ci = cb[ci_cur ^ 1];
+            ci.ok = false;
+            if (try_merge(u, pools, w, cur, cc, r, ci, mg)) {
+                cur = mg;
+                cc.ok = false;
+                unverified += bit;
+                continue;
+            }
+            seg.push_back(cur);
+            cur = r;
+            ci_cur ^= 1;
+            if (!bit) continue;
+            refine_seg();
+            if (!fold_cut(r.start, r.mlen, mx)) {
+                ++unverified;
+                continue;
+            }
+            close_seg();
+            if (j >= ne) break;
+            ++cuts;
+        }
+        if (j >= n) {   // the end of the records closes the last segment
+            seg.push_back(cur);
+            refine_seg();
+            close_seg();
+            j = n;
+        }
+        n_cuts.fetch_add(cuts, std::memory_order_relaxed);
+        n_unverified.fetch_add(unverified, std::memory_order_relaxed);
+        n_folded.fetch_add(folded, std::memory_order_relaxed);
+        n_collapsed.fetch_add(collapsed, std::memory_order_relaxed);
+        return j;
+    };
+    auto task = [&](int64_t k, int w) {
+        if (k == inj) fail(BWTMI_E_STATE, "injected failure in merge task %lld", (long long)k);
+        const auto a = clk::now();
+        const int64_t ne = nom(k + 1);
+        src.wait(ne);
+        int64_t i = nom(k);
+        Item r;
+        while (i < ne && !src.get(i, r)) ++i;
+        if (i >= ne) return;   // no cut in the range: an earlier task folds through it
+        first[(size_t)k] = i;
+        stop[(size_t)k] = fold_range(i, ne, w, surv[(size_t)k]);
+        if (stats_on()) cms[(size_t)k] = std::chrono::duration<double, std::milli>(clk::now() - a).count();
+    };
+    int64_t redone = 0;
+    {
+        BWTMI_STAGE("bwtmi:merge");
+        parallel_items(K, nt, task);   // dynamic: the tasks' costs are uneven
+        // reconcile: a task whose start the fold before it ran through (the bit
+        // there was not verified) is folded again from where that fold stopped
+        int64_t pos = 0;
+        for (int64_t k = 0; k < K; ++k) {
+            if (first[(size_t)k] < 0 || first[(size_t)k] == pos) {
+                if (first[(size_t)k] >= 0) pos = stop[(size_t)k];
+                continue;
+            }
+            surv[(size_t)k].clear();
+            ++redone;
+            if (pos < nom(k + 1)) pos = fold_range(pos, nom(k + 1), 0, surv[(size_t)k]);
+        }
+        if (pos < n) {
+            (void)fold_range(pos, n, 0, surv[(size_t)K]);
+            ++redone;
+        }
+    }
+    const auto t1 = clk::now();
+    // the survivors materialised at their offsets.  Every slot is constructed
+    // whatever throws: a task whose materialize throws constructs the rest of
+    // its slots before it reports, and the tasks after it only construct
+    // theirs, so the vector's destructor never meets a raw slot.
+    BWTMI_STAGE("bwtmi:refine..filter");
+    const int64_t KS = K + 1;
+    std::vector<int64_t> cnt((size_t)KS + 1, 0);
+    for (int64_t k = 0; k < KS; ++k) cnt[(size_t)k + 1] = cnt[(size_t)k] + (int64_t)surv[(size_t)k].size();
+    {
+        DeferConstruct raw;   // constructed below, in parallel
+        out.resize((size_t)cnt[(size_t)KS]);
+    }
+    static_assert(std::is_nothrow_default_constructible<Rec>::value, "Rec() must not throw");
+    std::atomic<bool> failed{false};
+    std::exception_ptr err;
+    std::mutex err_mu;
+    parallel_items(KS, nt, [&](int64_t t, int) {
+        const int64_t q1 = cnt[(size_t)t + 1];
+        int64_t o = cnt[(size_t)t];   // slots [cnt[t], o) are constructed
+        if (!failed.load(std::memory_order_relaxed)) {
+            try {
+                const std::vector<Item> &sv = surv[(size_t)t];
+                for (size_t j = 0; j < sv.size(); ++j) {
+                    if (j + 8 < sv.size() && sv[j + 8].xp) __builtin_prefetch(sv[j + 8].x());
+                    ::new ((void *)&out[(size_t)o]) Rec();
+                    ++o;
+                    materialize(u, sv[j], shift, out[(size_t)o - 1]);
+                }
+            } catch (...) {
+                failed.store(true, std::memory_order_relaxed);
+                std::lock_guard<std::mutex> lk(err_mu);
+                if (!err) err = std::current_exception();
+            }
+        }
+        for (; o < q1; ++o) ::new ((void *)&out[(size_t)o]) Rec();
+    });
+    if (err) std::rethrow_exception(err);
+    const auto t2 = clk::now();
+    auto d = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    if (stats_on()) {
+        double sum = 0, mx = 0;
+        for (double v : cms) { sum += v; mx = std::max(mx, v); }
+        std::fprintf(stderr, "  merge+refine+collapse+filter in one pass %.1f ms (K=%lld, task sum %.1f max %.1f ms): %lld hits, "
+                     "%lld cuts (%lld bits unverified, %lld tasks folded again), merge -> %lld, collapse -> %lld, "
+                     "filter -> %lld; materialise %.1f ms\n",
+                     d(t0, t1), (long long)K, sum, mx, (long long)n, (long long)n_cuts.load(), (long long)n_unverified.load(),
+                     (long long)redone, (long long)n_folded.load(), (long long)n_collapsed.load(), (long long)cnt[(size_t)KS],
+                     d(t1, t2));
+    }
+    if (ms) {
+        ms[2] += d(t0, t1);
+        ms[3] += d(t1, t2);
+    }
+}
+
 void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vector<HitVec> &raw,
                   std::vector<ScreenedVec> &shits, RecVec &out, double *ms, int nt) {
     using clk = std::chrono::steady_clock;
     auto t0 = clk::now();
     UnitCtx u{&job, job.params.min_copies};
     Pools pools(std::max(1, nt));
+    // one contig, strict hits only: the fold to the filter in one pass over cut
+    // segments (fold_cuts; BWTMI_FOLD_CUTS=0: the general path).  Units of
+    // several contigs and records that carry an Extra on input (Tier 3) stay on
+    // the general path: screen_reach bounds records built from one contig's
+    // strict hits only
+    const bool cuts_on = knob(KN_FOLD_CUTS) != 0 && chroms.size() == 1;
     // 1. nested suppression per chromosome (bwt.py:3928), concatenated in
     //    chromosome order, stable-sorted by (start, end).
     //    Hits the device already screened (nested.hip) arrive kept, sorted and
@@ -1579,6 +1898,19 @@ void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vecto
         const bool t3 = mine && (size_t)c < job.t3.size() && !job.t3[(size_t)c].empty();
         if (scr && !t3) {
             const ScreenedVec &sh = shits[(size_t)c];
+            if (cuts_on) {   // the records never enter a shared array
+                if (knob(KN_DEVICE_CHECKS)) check_device_cuts(u, sh, nt);
+                CutSrc src;
+                src.sh = &sh;
+                src.chrom = c;
+                src.n = sh.size();
+                auto t1 = clk::now();
+                fold_cuts(u, pools, src, nt, job.contigs[(size_t)c].trim_left, out, ms);
+                ScreenedVec().swap(shits[(size_t)c]);
+                HitVec().swap(raw[(size_t)c]);
+                if (ms) ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+                return;
+            }
             recs.resize(sh.size());   // NoInit: filled by fill_fn
             fill_fn = [&recs, &sh, c](int64_t a, int64_t b) {
                 sh.wait(b);   // the scan's download of these hits may still be landing
@@ -1590,6 +1922,7 @@ void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vecto
             };
         }
     }
+    bool strict_only = true;   // no input record carries an Extra
     for (int32_t c : chroms) {
         if (fill_fn) break;   // the fused path above
         auto &h = raw[(size_t)c];
@@ -1623,6 +1956,7 @@ void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vecto
         if (mine && (size_t)c < job.t3.size() && !job.t3[(size_t)c].empty()) {
             if (scr) fail(BWTMI_E_STATE, "contig %d holds device-screened hits and Tier 3 records", (int)c);
             for (const Rec &r : job.t3[(size_t)c]) items.push_back(item_of_rec(pools, r));
+            strict_only = false;
         }
         if (!scr) items = suppress_nested(items, 0.5, nt);
         if (recs.empty()) recs.swap(items);
@@ -1633,6 +1967,28 @@ void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vecto
     // 2. dedup (bwt.py:3189-3220)
     if (!presorted) dedup_sorted(u, recs);
     auto t2 = clk::now();
+    if (cuts_on && !fill_fn && strict_only && !recs.empty()) {   // host-screened hits: their cut bits, then the one pass
+        const std::vector<uint8_t> cut =
+            host_cuts((int64_t)recs.size(), u.min_copies, false, nt, [&](int64_t k, int64_t &s, int64_t &e, int64_t &m) {
+                const Item &r = recs[(size_t)k];
+                s = r.start;
+                e = r.end;
+                m = r.mlen;
+            });
+        CutSrc src;
+        src.recs = &recs;
+        src.cut = cut.data();
+        src.chrom = chroms[0];
+        src.n = (int64_t)recs.size();
+        const auto t_bits = clk::now();
+        fold_cuts(u, pools, src, nt, job.contigs[(size_t)chroms[0]].trim_left, out, ms);
+        if (ms) {
+            ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+            ms[1] += std::chrono::duration<double, std::milli>(t2 - t1).count();
+            ms[2] += std::chrono::duration<double, std::milli>(t_bits - t2).count();   // the cut bits
+        }
+        return;
+    }
     // 3. merge adjacent (bwt.py:3222-3289)
     OutChunks oc;
     {
