@@ -74,6 +74,36 @@ class LocateResult:
         return self.positions[a:b], self.mismatches[a:b], self.strand[a:b]
 
 
+class SmemResult:
+    """SMEMs of BWTCore.smem_batch: `offsets` (int64[nq + 1]) into `qstart`,
+    `qend` (int32), `strand` (uint8, 0 = '+', 1 = '-') and `count` (int64);
+    `pos_offsets` (int64[nsmem + 1]) into `positions` (int64, ascending per
+    SMEM, empty where count > max_occ).  result[i] = (qstart, qend, strand,
+    count, positions per SMEM) of query i, its SMEMs by (strand, qstart).
+    `positions_total` is the call's position count (what max_positions caps),
+    `work` the sum of the matching statistics (the search's rank steps)."""
+
+    __slots__ = ("offsets", "qstart", "qend", "strand", "count", "pos_offsets", "positions", "positions_total",
+                 "work")
+
+    def __init__(self, offsets, qstart, qend, strand, count, pos_offsets, positions, positions_total=0, work=0):
+        self.offsets, self.qstart, self.qend, self.strand, self.count = offsets, qstart, qend, strand, count
+        self.pos_offsets, self.positions = pos_offsets, positions
+        self.positions_total, self.work = positions_total, work
+
+    def __len__(self):
+        return self.offsets.size - 1
+
+    def __getitem__(self, i: int):
+        if not -len(self) <= i < len(self):
+            raise IndexError(i)
+        i %= len(self)
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        po = self.pos_offsets
+        return (self.qstart[a:b], self.qend[a:b], self.strand[a:b], self.count[a:b],
+                [self.positions[int(po[j]):int(po[j + 1])] for j in range(a, b)])
+
+
 class BWTCore:
     BASE_TO_BITS = {"A": 0, "C": 1, "G": 2, "T": 3, "N": 0}
     BITS_TO_BASE = {0: "A", 1: "C", 2: "G", 3: "T"}
@@ -297,6 +327,49 @@ class BWTCore:
                                 take(strand, np.uint8, n), cand.value)
         finally:
             for p in (hoff, pos, mm, strand):
+                lib().bwtmi_free(p)
+
+    def smem_batch(self, queries: Sequence[Union[str, bytes]], min_len: int = 1, both_strands: bool = False,
+                   max_occ: Optional[int] = None, max_positions: Optional[int] = None) -> "SmemResult":
+        """The super-maximal exact matches (>= `min_len` bytes) of every query
+        against the index text, on the text's strand or on both, with their
+        occurrences when there are at most `max_occ` (default 1024), found on
+        the device (include/bwtmi.h, bwtmi_index_smem_batch, states the
+        contract).  ValueError for an empty query, one longer than 1024 bytes
+        or min_len < 1; BwtmiError with the position count when it exceeds
+        max_positions (default 2^27)."""
+        for name, v in (("max_occ", max_occ), ("max_positions", max_positions)):
+            if v is not None and int(v) <= 0:
+                raise ValueError(f"{name} must be positive")
+        enc = [q.encode("utf-8") if isinstance(q, str) else bytes(q) for q in queries]
+        off = np.zeros(len(enc) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(e) for e in enc]) if enc else 0
+        blob = np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8)
+        nq = off.size - 1
+        ptrs = [C.c_void_p() for _ in range(7)]
+        ns, npos, total, work = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        rc = lib().bwtmi_index_smem_batch(self._ctx, self._h, blob.ctypes.data_as(C.c_void_p),
+                                          off.ctypes.data_as(C.c_void_p), nq, int(min_len), 1 if both_strands else 0,
+                                          0 if max_occ is None else int(max_occ),
+                                          0 if max_positions is None else int(max_positions),
+                                          *[C.byref(p) for p in ptrs], C.byref(ns), C.byref(npos), C.byref(total),
+                                          C.byref(work))
+        if rc == -1:   # BWTMI_E_ARG
+            msg = lib().bwtmi_last_error()
+            raise ValueError(msg.decode(errors="replace") if msg else "bad argument")
+        check(rc)
+        try:
+            def take(p, dtype, count):
+                if not count:
+                    return np.zeros(0, dtype=dtype)
+                return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))),
+                                             shape=(count,)).copy()
+            n = ns.value
+            return SmemResult(take(ptrs[0], np.int64, nq + 1), take(ptrs[1], np.int32, n), take(ptrs[2], np.int32, n),
+                              take(ptrs[3], np.uint8, n), take(ptrs[4], np.int64, n), take(ptrs[5], np.int64, n + 1),
+                              take(ptrs[6], np.int64, npos.value), total.value, work.value)
+        finally:
+            for p in ptrs:
                 lib().bwtmi_free(p)
 
     def _get_suffix_position(self, sa_index: int) -> int:

@@ -530,6 +530,45 @@ int bwtmi_index_locate_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *pa
     });
 }
 
+int bwtmi_index_smem_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                           int32_t min_len, uint32_t flags, int64_t max_occ, int64_t max_positions, int64_t **smem_off,
+                           int32_t **qstart, int32_t **qend, uint8_t **strand, int64_t **count, int64_t **pos_off,
+                           int64_t **pos, int64_t *nsmem, int64_t *npos, int64_t *positions_total, int64_t *work) {
+    return guard([&] {
+        CHECK_ARG(ctx && idx && off && smem_off && qstart && qend && strand && count && pos_off && pos && nsmem && npos &&
+                      nq >= 0,
+                  "bad argument");
+        CHECK_ARG(qs || nq == 0, "null queries");
+        *smem_off = *count = *pos_off = *pos = nullptr;
+        *qstart = *qend = nullptr;
+        *strand = nullptr;
+        *nsmem = *npos = 0;
+        if (positions_total) *positions_total = 0;
+        if (work) *work = 0;
+        CHECK_ARG((flags & ~BWTMI_SMEM_BOTH_STRANDS) == 0, "unknown smem flag");
+        use(ctx->c);
+        SmemResult r;
+        try {
+            index_smem_batch(ctx->c, idx->d, qs, off, nq, min_len, (flags & BWTMI_SMEM_BOTH_STRANDS) != 0, max_occ,
+                             max_positions, r);
+        } catch (...) {
+            if (positions_total) *positions_total = r.positions_total;   // the count a tripped cap reports
+            throw;
+        }
+        if (positions_total) *positions_total = r.positions_total;
+        if (work) *work = r.work;
+        *smem_off = malloc_copy(r.smem_off);
+        *qstart = malloc_copy(r.qstart);
+        *qend = malloc_copy(r.qend);
+        *strand = malloc_copy(r.strand);
+        *count = malloc_copy(r.count);
+        *pos_off = malloc_copy(r.pos_off);
+        *pos = malloc_copy(r.pos);
+        *nsmem = (int64_t)r.qstart.size();
+        *npos = (int64_t)r.pos.size();
+    });
+}
+
 static LibParams lib_params(const bwtmi_lib_params *p) {
     LibParams q;
     if (p) {

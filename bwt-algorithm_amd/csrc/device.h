@@ -432,6 +432,47 @@ struct LocateResult {
 };
 void index_locate_batch(Ctx &c, DeviceIndex *ix, const uint8_t *pats, const int64_t *off, int64_t npat,
                         int32_t max_mismatch, bool both_strands, int64_t max_candidates, LocateResult &out);
+
+// ----- batched SMEM seeding of reads (smem.hip; contract in bwtmi.h)
+constexpr int64_t kSmemMaxQuery = 1024;
+constexpr int64_t kSmemDefaultMaxOcc = 1024;
+// one searched string (a query, or its reverse complement): its bytes start at
+// qoff of the uploaded bytes, which is also its first lane
+struct SmemStr {
+    int64_t qoff;
+    int32_t query;
+    uint32_t info;   // m (11 bits) | strand << 11
+};
+static_assert(kSmemMaxQuery <= 1024, "SmemStr::info field widths");
+// Lane g is byte g of the strings laid back to back: its string (str: ns
+// entries ascending by qoff, str[0].qoff = 0) and its end e in 1..m.  A '+'
+// string takes its ends ascending, a '-' string descending, so that lane order
+// is (query, strand, qstart) order.
+__device__ __forceinline__ int smem_lane(const SmemStr *__restrict__ str, int64_t ns, int64_t g, SmemStr &s) {
+    int64_t lo = 0, hi = ns;   // str[lo].qoff <= g < str[hi].qoff
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (str[mid].qoff <= g) lo = mid;
+        else hi = mid;
+    }
+    s = str[lo];
+    const int m = (int)(s.info & 2047u), t = (int)(g - s.qoff);
+    return (s.info >> 11) & 1u ? m - t : t + 1;
+}
+// matching statistics of every (string, end) lane, left on the device (index.hip);
+// max_steps = the sum of the lanes' ends, the bound of the rank steps (byte model)
+void index_smem_ms_device(Ctx &c, DeviceIndex *, const uint8_t *d_q, const SmemStr *d_str, int64_t ns, int64_t nl,
+                          double max_steps, int32_t *d_ell, int64_t *d_row0, int64_t *d_width);
+struct SmemResult {
+    std::vector<int64_t> smem_off;         // nq + 1
+    std::vector<int32_t> qstart, qend;     // per SMEM
+    std::vector<uint8_t> strand;
+    std::vector<int64_t> count;
+    std::vector<int64_t> pos_off, pos;     // nsmem + 1 offsets; positions
+    int64_t positions_total = 0, work = 0;
+};
+void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq, int32_t min_len,
+                      bool both_strands, int64_t max_occ, int64_t max_positions, SmemResult &out);
 // Tier2LCPFinder.find_long_repeats -> _find_repeats_simple (bwt.py:2097-2106, 2177-2498)
 void simple_scan_device(Ctx &c, DeviceIndex *ix, const LibParams &p, const std::vector<int64_t> &seen_pairs,
                         int32_t chrom, RecVec &out);

@@ -476,8 +476,20 @@ __device__ __forceinline__ int code5(uint8_t ch) {
     }
 }
 
-// backward search over the packed rank, one pattern per lane: each step is
-// two 32-byte block loads and two popcounts.  The lane's search of pats[a, b)
+// one step of the backward search over the packed rank (two 32-byte block
+// loads and two popcounts): [sp, ep] of a string X -> [sp, ep] of ch X; false
+// (sp, ep as they were) when ch X does not occur
+__device__ __forceinline__ bool bstep2(const FM2View &f, uint8_t ch, int64_t &sp, int64_t &ep) {
+    const int c = code5(ch);
+    if (c < 0 || f.tot[c] == 0) return false;
+    const int64_t s = f.C[c] + rank2(f, c, sp), e = f.C[c] + rank2(f, c, ep + 1) - 1;
+    if (s > e) return false;
+    sp = s;
+    ep = e;
+    return true;
+}
+
+// backward search over the packed rank, one pattern per lane: the lane's search of pats[a, b)
 // (shared by k_bsearch2 and the locate seed search, k_loc_seed2)
 __device__ __forceinline__ void bsearch2_lane(const FM2View &f, const uint8_t *__restrict__ pats, int64_t a, int64_t b,
                                               int64_t &sp, int64_t &ep) {
@@ -487,17 +499,12 @@ __device__ __forceinline__ void bsearch2_lane(const FM2View &f, const uint8_t *_
         ep = f.n - 1;
         return;
     }
-    int c = code5(pats[b - 1]);
+    const int c = code5(pats[b - 1]);
     if (c >= 0 && f.tot[c] > 0) {
         sp = f.C[c];
         ep = sp + f.tot[c] - 1;
-        for (int64_t i = b - 2; i >= a; --i) {
-            c = code5(pats[i]);
-            if (c < 0 || f.tot[c] == 0) { sp = ep = -1; break; }
-            sp = f.C[c] + rank2(f, c, sp);
-            ep = f.C[c] + rank2(f, c, ep + 1) - 1;
-            if (sp > ep) { sp = ep = -1; break; }
-        }
+        for (int64_t i = b - 2; i >= a; --i)
+            if (!bstep2(f, pats[i], sp, ep)) { sp = ep = -1; break; }
     }
 }
 
@@ -545,6 +552,16 @@ __device__ int64_t d_rank(const FMView &f, uint8_t c, int64_t pos) {
     return base;
 }
 
+// one step over the byte Occ (bstep2's contract)
+__device__ __forceinline__ bool bstep(const FMView &f, uint8_t c, int64_t &sp, int64_t &ep) {
+    if (f.tot[c] == 0) return false;
+    const int64_t s = f.C[c] + d_rank(f, c, sp), e = f.C[c] + d_rank(f, c, ep + 1) - 1;
+    if (s > e) return false;
+    sp = s;
+    ep = e;
+    return true;
+}
+
 // the lane's search of pats[a, b) (shared by k_bsearch and k_loc_seed)
 __device__ __forceinline__ void bsearch_lane(const FMView &f, const uint8_t *__restrict__ pats, int64_t a, int64_t b,
                                              int64_t &sp, int64_t &ep) {
@@ -554,17 +571,12 @@ __device__ __forceinline__ void bsearch_lane(const FMView &f, const uint8_t *__r
         ep = f.n - 1;
         return;
     }
-    uint8_t c = pats[b - 1];
+    const uint8_t c = pats[b - 1];
     if (f.tot[c] > 0) {
         sp = f.C[c];
         ep = sp + f.tot[c] - 1;
-        for (int64_t i = b - 2; i >= a; --i) {
-            c = pats[i];
-            if (f.tot[c] == 0) { sp = ep = -1; break; }
-            sp = f.C[c] + d_rank(f, c, sp);
-            ep = f.C[c] + d_rank(f, c, ep + 1) - 1;
-            if (sp > ep) { sp = ep = -1; break; }
-        }
+        for (int64_t i = b - 2; i >= a; --i)
+            if (!bstep(f, pats[i], sp, ep)) { sp = ep = -1; break; }
     }
 }
 
@@ -586,6 +598,71 @@ __global__ void k_loc_seed(FMView f, const uint8_t *__restrict__ pats, const int
     bsearch_lane(f, pats, off[p], off[p + 1], sp, ep);
     row0[p] = sp < 0 ? 0 : sp;
     width[p] = sp < 0 ? 0 : ep - sp + 1;
+}
+
+// ---- matching statistics of the SMEM search (smem.hip), one lane per
+// (searched string, end e) (smem_lane, device.h).  The lane extends Q[e - 1]
+// leftwards while the interval stays non-empty: ell = l(e), row0 / width =
+// the SA interval of Q[e - l, e) (width 0 when l = 0).  The lanes of a
+// wave are consecutive ends of one string: at step j they read consecutive
+// bytes and their l differ by at most their distance.  The loops end on the
+// lane's own interval only.
+__global__ __launch_bounds__(256) void k_smem_ms2(FM2View f, const uint8_t *__restrict__ q,
+                                                  const SmemStr *__restrict__ str, int64_t ns, int64_t nl,
+                                                  int32_t *__restrict__ ell, int64_t *__restrict__ row0,
+                                                  int64_t *__restrict__ width) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nl) return;
+    SmemStr s;
+    const int e = smem_lane(str, ns, g, s);   // device.h
+    const uint8_t *__restrict__ qq = q + s.qoff;
+    int l = 0;
+    int64_t sp = 0, ep = -1;
+    const int c = code5(qq[e - 1]);
+    if (c >= 0 && f.tot[c] > 0) {
+        sp = f.C[c];
+        ep = sp + f.tot[c] - 1;
+        l = 1;
+        // the text's one '$' is its last byte: '$' X (X not empty) occurs nowhere, and the
+        // step would find it wrapped round the end of the text
+        for (int i = e - 2; i >= 0 && qq[i] != '$' && bstep2(f, qq[i], sp, ep); --i) ++l;
+    }
+    ell[g] = l;
+    row0[g] = sp;
+    width[g] = ep - sp + 1;
+}
+
+__global__ __launch_bounds__(256) void k_smem_ms(FMView f, const uint8_t *__restrict__ text,
+                                                 const uint8_t *__restrict__ q, const SmemStr *__restrict__ str,
+                                                 int64_t ns, int64_t nl, int32_t *__restrict__ ell,
+                                                 int64_t *__restrict__ row0, int64_t *__restrict__ width) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nl) return;
+    SmemStr s;
+    const int e = smem_lane(str, ns, g, s);   // device.h
+    const uint8_t *__restrict__ qq = q + s.qoff;
+    int l = 0;
+    int64_t sp = 0, ep = -1;
+    const uint8_t c = qq[e - 1], last = text[f.n - 1];
+    if (f.tot[c] > 0) {
+        sp = f.C[c];
+        ep = sp + f.tot[c] - 1;
+        l = 1;
+        for (int i = e - 2; i >= 0; --i) {
+            const uint8_t b = qq[i];
+            int64_t s2 = sp, e2 = ep;
+            if (!bstep(f, b, s2, e2)) break;
+            // the first row of the text's last byte is the suffix made of that byte alone:
+            // 'b X' (X not empty) found there wraps round the end of the text
+            if (b == last && s2 == f.C[b] && ++s2 > e2) break;
+            sp = s2;
+            ep = e2;
+            ++l;
+        }
+    }
+    ell[g] = l;
+    row0[g] = sp;
+    width[g] = ep - sp + 1;
 }
 
 inline unsigned blocks(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
@@ -1037,6 +1114,30 @@ void index_seed_search_device(Ctx &c, DeviceIndex *ix, const uint8_t *d_pats, co
         const FMView f = fm_view(c, ix);
         KLAUNCH("k_loc_seed", bytes, k_loc_seed, dim3(blocks(np)), dim3(256), 0, st, f, d_pats, d_off, np, d_row0,
                 d_width);
+    }
+    HIPCHECK(hipGetLastError());
+}
+
+// The SMEM search's matching statistics (smem.hip): nl lanes over the ns
+// strings of d_str, d_q their bytes; l(e), the first SA row and the width of
+// every lane stay on the device.  The same choice of rank path as above; uses
+// the S_MISC3 slot (byte-Occ tables).
+void index_smem_ms_device(Ctx &c, DeviceIndex *ix, const uint8_t *d_q, const SmemStr *d_str, int64_t ns, int64_t nl,
+                          double max_steps, int32_t *d_ell, int64_t *d_row0, int64_t *d_width) {
+    if (nl <= 0) return;
+    hipStream_t st = c.stream;
+    // a model, not a count: l(e) is not known before the launch, so every lane
+    // is taken to run its e steps (max_steps = their sum; a read copied from the
+    // text does), a byte and two 32-byte rank blocks each, 20 bytes out.  The
+    // steps really taken are the call's `work`.
+    const double bytes = max_steps * 65.0 + (double)nl * 20.0;
+    if (ix->has_fm2 && !knob(KN_FM_BYTES)) {
+        KLAUNCH("k_smem_ms2", bytes, k_smem_ms2, dim3(blocks(nl)), dim3(256), 0, st, fm2_view(ix), d_q, d_str, ns, nl,
+                d_ell, d_row0, d_width);
+    } else {
+        const FMView f = fm_view(c, ix);
+        KLAUNCH("k_smem_ms", bytes, k_smem_ms, dim3(blocks(nl)), dim3(256), 0, st, f, ix->text.as<uint8_t>(), d_q, d_str,
+                ns, nl, d_ell, d_row0, d_width);
     }
     HIPCHECK(hipGetLastError());
 }

@@ -221,6 +221,58 @@ int bwtmi_index_locate_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *pa
                              int64_t npat, int32_t max_mismatch, uint32_t flags, int64_t max_candidates,
                              int64_t **hit_off, int64_t **pos, uint8_t **mm, uint8_t **strand, int64_t *nhits,
                              int64_t *candidates);
+/* Batched SMEM seeding: the super-maximal exact matches of every query against
+ * the index text, on one or both strands, with where they occur (not in the
+ * reference).  T = the index text (n bytes, sentinel included), query q is
+ * Q = qs[off[q] .. off[q+1]) of m bytes, 1 <= m <= 1024.  "Occurs" is plain
+ * substring equality in T, bytes compared as backward_search compares them: no
+ * case folding, 'N' and '$' are ordinary bytes, a byte absent from T occurs
+ * nowhere.  No match wraps round the end of T: "$A" does not occur in "ACGT$"
+ * (bwtmi_backward_search_batch, as the reference, reports that cyclic match).
+ *   l(e)     matching statistics, e in 1..m: the largest l <= e such that
+ *            Q[e-l, e) occurs in T; 0 when Q[e-1] does not occur.  Always
+ *            l(e+1) <= l(e) + 1.
+ *   SMEM     [s, e) with s = e - l(e) is an SMEM of Q when l(e) >= min_len and
+ *            (e == m or l(e+1) <= l(e)); equivalently Q[s,e) occurs in T and
+ *            neither Q[s-1,e) nor Q[s,e+1) does.  Within one strand the SMEMs
+ *            of a query have strictly increasing s and e.
+ *   strands  with BWTMI_SMEM_BOTH_STRANDS the same search runs on Q' =
+ *            revcomp(Q) (the locate byte rule: A<->T, C<->G, every other byte
+ *            unchanged, reversed).  An SMEM [s, e) of Q' is reported with strand
+ *            1 and the coordinates of the original query, qstart = m - e, qend
+ *            = m - s.  A query equal to its own reverse complement is searched
+ *            on '+' only.
+ *   count    the occurrences of the SMEM's string in T (the width of its SA
+ *            interval).  count <= max_occ (<= 0: the default 1024): every
+ *            occurrence start, ascending, in pos[pos_off[i] .. pos_off[i+1]);
+ *            on strand 1 the forward-text start of the Q' match.  count >
+ *            max_occ: the SMEM is still reported, with its count and an empty
+ *            slice.
+ *   cap      the call's position count is the sum of count over the SMEMs with
+ *            count <= max_occ.  Above max_positions (<= 0: the default 2^27)
+ *            the call fails with BWTMI_E_NOMEM and the count in the message;
+ *            nothing is truncated.  *positions_total (may be NULL) receives the
+ *            count either way.
+ *   order    queries in batch order, smem_off[nq + 1] their offsets into the
+ *            SMEM arrays; a query's SMEMs by (strand, qstart).
+ *   work     *work (may be NULL) = the sum of l(e) over every searched string
+ *            and every e: the rank steps the search is made of.
+ *   errors   BWTMI_E_ARG: an empty query, m > 1024, min_len < 1, an unknown
+ *            flag; every output pointer is then NULL and every count 0.  nq = 0
+ *            is legal (smem_off = [0], pos_off = [0]), and so is min_len > m (no
+ *            SMEMs).
+ * One lane per end costs the sum of l(e) rank steps, m^2 / 2 for a read copied
+ * from the text: hence the 1024-byte limit.  Longer reads need a bidirectional
+ * index, which this library does not have.
+ * The seven arrays are malloc'd (never NULL on success; free with bwtmi_free):
+ * smem_off[nq + 1]; qstart, qend, strand, count[*nsmem]; pos_off[*nsmem + 1];
+ * pos[*npos]. */
+#define BWTMI_SMEM_BOTH_STRANDS 1u
+int bwtmi_index_smem_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                           int32_t min_len, uint32_t flags, int64_t max_occ, int64_t max_positions,
+                           int64_t **smem_off, int32_t **qstart, int32_t **qend, uint8_t **strand, int64_t **count,
+                           int64_t **pos_off, int64_t **pos, int64_t *nsmem, int64_t *npos,
+                           int64_t *positions_total, int64_t *work);
 
 /* ------------------------------------------------------------ repeat job
  * Replaces the per-contig worker result handling and the post-processing of
