@@ -56,6 +56,8 @@ _SIGS = {
     "bwtmi_kernel_stats_filter": (C.c_int, [_P, C.c_char_p]),
     "bwtmi_strict_scan": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.POINTER(C.POINTER(Hit)), C.POINTER(C.c_int64)]),
+    "bwtmi_screen_hits": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
+                                    C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "bwtmi_index_build": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(_P)]),
     "bwtmi_index_free": (C.c_int, [_P]),
     "bwtmi_index_size": (C.c_int64, [_P]),
@@ -305,6 +307,27 @@ def kernel_stats(h, enable: bool = True, reset: bool = True) -> dict:
 def kernel_stats_filter(h, name: str = "") -> None:
     """Time only the launches named `name` ("" = every launch)."""
     check(lib().bwtmi_kernel_stats_filter(h, name.encode() if name else None))
+
+
+def screen_hits(h, hits, text_len: int, min_copies: int = 3, drop: bool = False, maxlen: int = -1):
+    """The device screen (bwtmi_screen_hits) on hits = int64[k,5] rows (start, end,
+    unit_len, prim_len, copies): int64[j,4] rows (start, len, prim, cut) of the
+    survivors in screen order."""
+    import numpy as np
+    hits = np.asarray(hits, dtype=np.int64).reshape(-1, 5)
+    arr = np.zeros(max(len(hits), 1), dtype=[("start", "<i8"), ("end", "<i8"), ("unit_len", "<i4"),
+                                             ("prim_len", "<i4"), ("copies", "<i8")])
+    assert arr.dtype.itemsize == C.sizeof(Hit)
+    for k, name in enumerate(arr.dtype.names):
+        arr[name][:len(hits)] = hits[:, k]
+    out, n = C.c_void_p(), C.c_int64(0)
+    check(lib().bwtmi_screen_hits(h, arr.ctypes.data_as(C.c_void_p), len(hits), int(text_len), int(min_copies),
+                                  int(bool(drop)), int(maxlen), C.byref(out), C.byref(n)))
+    try:
+        rows = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_int64)), shape=(max(n.value, 1) * 4,))
+        return rows[:n.value * 4].reshape(-1, 4).copy()
+    finally:
+        lib().bwtmi_free(out)
 
 
 def host_info() -> dict:

@@ -428,6 +428,55 @@ int bwtmi_strict_scan(bwtmi_ctx *ctx, const uint8_t *seq, int64_t n, int32_t min
     });
 }
 
+// the device screen on a caller's hit list (tests, embedders): the hits go to
+// the slot the scan leaves its own in, screen_hits_device runs as it does there
+int bwtmi_screen_hits(bwtmi_ctx *ctx, const bwtmi_hit *hits, int64_t n, int64_t text_len, int32_t min_copies,
+                      int32_t drop, int64_t maxlen, int64_t **out, int64_t *nout) {
+    return guard([&] {
+        CHECK_ARG(ctx && out && nout && (hits || n == 0) && n >= 0, "bad argument");
+        *out = nullptr;
+        *nout = 0;
+        CHECK_ARG(text_len >= 0 && min_copies >= 1 && maxlen >= -1, "bad argument");
+        // the level kernels index a bucket table by end >> 6: no span past text_len reaches them
+        int64_t longest = 0;
+        int32_t lmax = 1;
+        for (int64_t i = 0; i < n; ++i) {
+            const bwtmi_hit &h = hits[i];
+            if (h.start < 0 || h.end <= h.start || h.end > text_len || h.prim_len < 1)
+                fail(BWTMI_E_ARG, "hit %lld [%lld, %lld) prim %d outside 0 <= start < end <= %lld, prim >= 1",
+                     (long long)i, (long long)h.start, (long long)h.end, (int)h.prim_len, (long long)text_len);
+            longest = std::max(longest, h.end - h.start);
+            lmax = std::max(lmax, h.prim_len);
+        }
+        CHECK_ARG(maxlen < 0 || maxlen >= longest, "maxlen is below the longest span");
+        std::vector<int64_t> rows;
+        if (n > 0) {
+            Ctx &c = ctx->c;
+            use(c);
+            c.slot[S_HITS].ensure((size_t)n * sizeof(bwtmi_hit));
+            HIPCHECK(hipMemcpyAsync(c.slot[S_HITS].p, hits, (size_t)n * sizeof(bwtmi_hit), hipMemcpyHostToDevice,
+                                    c.stream));
+            ScreenedVec sv;
+            screen_hits_device(c, c.slot[S_HITS].as<bwtmi_hit>(), n, text_len, lmax, sv, maxlen, min_copies, drop != 0);
+            const int64_t nk = sv.size();
+            sv.wait(nk);
+            c.kresolve();
+            rows.resize((size_t)nk * 4);
+            for (int64_t k = 0; k < nk; ++k) {
+                int64_t s, len, prim;
+                const bool cut = sv.get(k, s, len, prim);
+                int64_t *r = rows.data() + 4 * k;
+                r[0] = s;
+                r[1] = len;
+                r[2] = prim;
+                r[3] = cut ? 1 : 0;
+            }
+        }
+        *nout = (int64_t)rows.size() / 4;
+        *out = malloc_copy(rows);
+    });
+}
+
 // ------------------------------------------------------------ index
 int bwtmi_index_build(bwtmi_ctx *ctx, const uint8_t *text, int64_t n, int32_t sa_sample, int32_t occ_sample,
                       uint32_t flags, bwtmi_index **out) {

@@ -118,6 +118,18 @@ int bwtmi_strict_scan(bwtmi_ctx *ctx, const uint8_t *seq, int64_t n, int32_t min
                       int32_t max_unit, int32_t max_mismatch, int32_t min_copies,
                       bwtmi_hit **hits, int64_t *nhits);
 
+/* The device screen (nested.hip) on a caller's hit list, as the scan runs it on
+ * its own hits: nested suppression, (start, end, prim desc) order, dedup, then
+ * the drop (drop != 0 and BWTMI_SCREEN_DROP) and the cut bits.
+ * Every hit must satisfy 0 <= start < end <= text_len and prim_len >= 1
+ * (unit_len and copies are not read); min_copies >= 1; BWTMI_E_ARG otherwise,
+ * before anything reaches the device.
+ * maxlen: the longest span if known, -1 to reduce it on the device.
+ * out: malloc'd, 4 int64 per surviving hit {start, len, prim, cut}; free with bwtmi_free. */
+int bwtmi_screen_hits(bwtmi_ctx *ctx, const bwtmi_hit *hits, int64_t n, int64_t text_len,
+                      int32_t min_copies, int32_t drop, int64_t maxlen,
+                      int64_t **out, int64_t *nout);
+
 /* ------------------------------------------------------------ FM index
  * Replaces BWTCore.__init__ (bwt.py:106-136): suffix array (212-264), BWT
  * (266-274), C table (276-286), Occ checkpoints (288-326), sampled SA
