@@ -906,6 +906,8 @@ void short_imperfect_device(Ctx &c, DeviceIndex *ix, const LibParams &p, const s
     const int64_t nw = (n + 63) / 64;
     std::vector<uint64_t> seed_bits((size_t)Lmax * (size_t)nw);   // k_seed_flags
     c.slot[S_IDX2].ensure(seed_bits.size() * 8);
+    int relaunches = 0;   // of k_extend, for a side list past its capacity (reported under the stats switch)
+    size_t unbinned = 0;  // side entries extended on the host (likewise)
     for (int64_t cap = 1 << 16;;) {
         c.slot[S_IDX1].ensure((size_t)cap * sizeof(ExtSide));
         HIPCHECK(hipMemsetAsync(c.slot[S_COUNTS].p, 0, 8, st));
@@ -918,10 +920,13 @@ void short_imperfect_device(Ctx &c, DeviceIndex *ix, const LibParams &p, const s
         HIPCHECK(hipStreamSynchronize(st));
         if ((int64_t)ns > cap) {   // the side list overflowed: again with room for all of it
             cap = (int64_t)ns;
+            ++relaunches;
             continue;
         }
         std::vector<ExtSide> side((size_t)ns);
-        if (stats) std::fprintf(stderr, "    text + extension kernel %.1f ms\n", ms_since(T0));
+        if (stats)
+            std::fprintf(stderr, "    text + extension kernel %.1f ms (%llu side entries, %d relaunches for their room)\n",
+                         ms_since(T0), ns, relaunches);
         SeedThr thr{};
         for (int L = 1; L <= Lmax; ++L) {
             const int64_t by_len = (std::max<int64_t>(0, p.min_array_length) + L - 1) / L;
@@ -941,6 +946,7 @@ void short_imperfect_device(Ctx &c, DeviceIndex *ix, const LibParams &p, const s
             int64_t s0, e0, c0;
             if (x.unbinned) {   // a symbol outside A C G N T: the scalar extension
                 extend_host(t, n, cs, L, s0, e0, c0);
+                ++unbinned;
             } else {
                 s0 = cs - (int64_t)x.left * L;
                 e0 = cs + L + (int64_t)x.right * L;
@@ -1151,16 +1157,17 @@ void short_imperfect_device(Ctx &c, DeviceIndex *ix, const LibParams &p, const s
         bool on;
         clk::time_point t0;
         double a, b, c;
-        size_t tasks, keep;
+        size_t tasks, keep, side, unbinned;
         const RecVec &out;
         ~Report() {
             if (on)
                 std::fprintf(stderr, "  short_imperfect: extension table %.1f, seeds/patterns %.1f, parallel seeds %.1f, "
-                             "serial walk + variations %.1f ms (%zu motifs, %zu candidate seeds, %zu records)\n", a,
+                             "serial walk + variations %.1f ms (%zu motifs, %zu candidate seeds, %zu records; "
+                             "%zu side entries, %zu unbinned)\n", a,
                              b - a, c - b, std::chrono::duration<double, std::milli>(clk::now() - t0).count() - c,
-                             tasks, keep, out.size());
+                             tasks, keep, out.size(), side, unbinned);
         }
-    } report{stats, T0, t_ext, t_prep, t_par, tasks.size(), nkeep, out};
+    } report{stats, T0, t_ext, t_prep, t_par, tasks.size(), nkeep, ext_side.size(), unbinned, out};
     // _find_tandems_fm_with_mismatches (bwt.py:2562-2695) in the reference's
     // order: only the seen test, the extension over the unseen shifts and the
     // motif length carried between seeds are order-dependent; a candidate
@@ -1542,7 +1549,7 @@ void simple_scan_device(Ctx &c, DeviceIndex *ix, const LibParams &P, const std::
     using clk = std::chrono::steady_clock;
     const bool stats = stats_on();
     double t_host = 0, t_dev = 0;
-    int64_t rounds = 0, nreq = 0;
+    int64_t rounds = 0, nreq = 0, nredo = 0;
     auto T0 = clk::now();
     std::vector<int64_t> req;        // (i, p | allow << 16)
     std::vector<int32_t> req_w;
@@ -1679,9 +1686,10 @@ void simple_scan_device(Ctx &c, DeviceIndex *ix, const LibParams &P, const std::
         for (int64_t q = 0; q < nr; ++q) {
             const int64_t i = req[(size_t)(2 * q)], pw = req[(size_t)(2 * q + 1)];
             SimRes r;
-            if (ovf[q])
+            if (ovf[q]) {
                 r = simple_extend_host(t, n, i, pw & 0xFFFF, (pw >> 16) & 1);
-            else
+                ++nredo;
+            } else
                 r = SimRes{res[5 * q], res[5 * q + 1], res[5 * q + 2], res[5 * q + 3], res[5 * q + 4]};
             walks[(size_t)req_w[(size_t)q]].look_res.push_back(r);   // requests of a walk: ascending, in order
         }
@@ -1690,8 +1698,9 @@ void simple_scan_device(Ctx &c, DeviceIndex *ix, const LibParams &P, const std::
         T0 = T1;
     }
     if (stats)
-        std::fprintf(stderr, "  simple scan: %lld walks, %lld rounds, %lld requests, host walk %.1f ms, device batches %.1f ms\n",
-                     (long long)walks.size(), (long long)rounds, (long long)nreq, t_host, t_dev);
+        std::fprintf(stderr, "  simple scan: %lld walks, %lld rounds, %lld requests, %lld host redos, host walk %.1f ms, "
+                     "device batches %.1f ms\n",
+                     (long long)walks.size(), (long long)rounds, (long long)nreq, (long long)nredo, t_host, t_dev);
     // replay in period order under the global cap: records of the accepted positions
     std::set<std::tuple<int64_t, int64_t, std::string>> seen;
     const std::string seq((const char *)t, (size_t)nt);

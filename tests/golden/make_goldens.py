@@ -740,6 +740,253 @@ def cmd_simple(a):
         json.dump(out, f, indent=0)
 
 
+# ------------------------------------------------- library finders: edge inputs
+SIMPLE_EDGE_PERIODS = (63, 64, 65, 100, 127, 128, 129, 191, 192, 193, 200)
+# text seeds other than 1000 + p: with those flanks the walk of a short period stops advancing on a
+# small array (it resumes at an array end that is not past its position) and uses up the reference's
+# 100,000 iterations before the long periods are walked with default parameters
+SIMPLE_EDGE_SEEDS = {191: 3191, 200: 3200}
+MANY_SYMBOLS = "ACGTRYKMSW"
+PLATEAU_KEYS = ("start", "end", "motif", "copies", "length", "tier", "confidence")
+
+
+def _period_text(p: int, sub: bool, copies: int, flank: int, seed: int) -> str:
+    """rnd(flank) + unit * copies + unit[:p // 2] + rnd(flank) over ACGT.  With
+    sub, every copy after the third and the half copy carry one substitution
+    (A<->C, G<->T), each in a column of its own: extension with mismatches
+    (period <= 64) takes those copies, exact extension (period >= 65) stops
+    after three, and the partial copy ends at the substitution either way.
+    With three copies the substitution sits at 85 % of the third: exact
+    extension keeps two copies and the array passes only as two copies plus a
+    partial one of >= 0.75."""
+    r = np.random.default_rng(seed)
+    B = "ACGT"
+
+    def rnd(k):
+        return "".join(B[i] for i in r.integers(0, 4, k))
+
+    left, unit, right = rnd(flank), rnd(p), rnd(flank)
+    arr = list(unit * copies + unit[:p // 2])
+    if sub:
+        swap = {"A": "C", "C": "A", "G": "T", "T": "G"}
+        for c in range(3, copies):
+            q = c * p + (7 + 13 * c) % p
+            arr[q] = swap[arr[q]]
+        if copies == 3:
+            q = 2 * p + (85 * p) // 100
+            arr[q] = swap[arr[q]]
+        q = copies * p + p // 4
+        arr[q] = swap[arr[q]]
+    return left + "".join(arr) + right
+
+
+def _flank(r, k: int, unit: str = "", nxt: str = "") -> str:
+    """k random ACGT bases that do not continue a neighbouring array: the last
+    is a transversion of the last base of `unit` (the array that follows) and
+    the first one of the first base of `nxt` (the array before).  A frame
+    shifted into the flank then cannot extend, and _is_maximal_fm -- which
+    drops an array whose neighbour base continues its consensus -- keeps it."""
+    B, tv = "ACGT", {"A": "C", "C": "A", "G": "T", "T": "G"}
+    s = [B[i] for i in r.integers(0, 4, k)]
+    if unit and s:
+        s[-1] = tv.get(unit[-1], "A")
+    if nxt and s:
+        s[0] = tv.get(nxt[0], "A")
+    return "".join(s)
+
+
+def _crafted_subs(seed: int, subs: str, n_segments: int = 16) -> str:
+    """_crafted_short with every substitution drawn from `subs`, behind a head of
+    hand-made arrays of 8- and 9-base units (looked up / located directly, no
+    padding needed) that put those bytes where the extension decides on them:
+    the byte in one copy only -- the 2nd of 6, where it ties with the base when
+    it is voted on (the smaller byte is the consensus), and the 4th of 7, where
+    it is outvoted; a unit that holds the byte in every copy (the byte's own
+    column); that unit with a base, or another of the bytes, there in one copy
+    (the byte keeps the majority: whether the odd copy stays is decided by
+    count_transversions_array's classes)."""
+    r = np.random.default_rng(seed)
+    out = ""
+    for j, x in enumerate(subs):
+        y = subs[(j + 1) % len(subs)]
+        for u, cps, odd, z in (("CAGTCCTA", 6, 1, x), ("GATTCAGCA", 7, 3, x),
+                               ("CT" + x + "GACTG", 6, -1, ""), ("GGC" + x + "TTACA", 6, -1, ""),
+                               ("G" + x + "CTTACA", 7, 3, "ATCG"[j % 4]), ("TC" + x + "AGGTCA", 7, 2, "T"),
+                               ("GT" + x + "CATCC", 7, 4, y if y != x else "C")):
+            arr = [u] * cps
+            if odd >= 0:
+                q = 4 if x not in u else u.index(x)
+                arr[odd] = u[:q] + z + u[q + 1:]
+            out += _flank(r, 17 + 2 * j, u) + "".join(arr) + _flank(r, 1, "", u)
+    trans = {"A": "G", "G": "A", "C": "T", "T": "C"}
+    B = "ACGT"
+    for _ in range(n_segments):
+        k = int(r.choice([2, 3, 4, 5, 6, 7, 8, 8, 9, 9]))
+        unit = "".join(B[i] for i in r.integers(0, 4, k))
+        out += _flank(r, int(r.integers(10, 50)), unit)
+        if r.random() < 0.6 and k < 8:
+            out += "A" * (8 - k)
+        arr = list(unit * int(r.integers(3, 14)))
+        for q in range(len(arr)):
+            v = r.random()
+            if v < 0.03:
+                arr[q] = subs[int(r.integers(0, len(subs)))]
+            elif v < 0.05:
+                arr[q] = trans[arr[q]]
+        out += "".join(arr)
+    return out
+
+
+def _dense_unbinned(n: int = 9000, seed: int = 31) -> str:
+    """'R' at every 4th base, so nearly every extension entry meets a byte
+    outside A C G N T, plus three clean arrays (8- and 9-base units, and a
+    3-base unit behind its A-padding), each between two 'R's."""
+    r = np.random.default_rng(seed)
+    B = "ACGT"
+    s = ["R" if q % 4 == 3 else B[int(x)] for q, x in enumerate(r.integers(0, 4, n))]
+    for pos, arr in [(1000, "CAGTTGCA" * 9), (4000, "GATCCTGAC" * 8), (7000, "AAAAA" + "CTG" * 14)]:
+        s[pos:pos + len(arr)] = arr
+        s[pos + len(arr)] = "R"
+    return "".join(s)
+
+
+def _library_edge_cases():
+    """name -> dict(finder, seq, params, tier1_seen): the inputs of
+    library_edges.json (the tests import this to build the same texts)."""
+    r = np.random.default_rng(2024)
+    B = "ACGT"
+
+    def rnd(k):
+        return "".join(B[i] for i in r.integers(0, 4, k))
+
+    cases = {}
+
+    def add(name, finder, seq, **params):
+        cases[name] = dict(finder=finder, seq=seq, params=params, tier1_seen=[])
+
+    # ---- short imperfect repeats
+    add("si_subs_N", "short_imperfect", _crafted_subs(41, "N", 26))
+    add("si_subs_NRY", "short_imperfect", _crafted_subs(42, "NRY", 14))
+    add("si_subs_low_high", "short_imperfect", _crafted_subs(43, "*a", 20))   # below 'A', above 'T'
+    u8, v8, u9, v9 = "ACGGTCAT", "TTCAGGCA", "GATCCTGAC", "CTTGACCAG"
+    # arrays from text position 0 and up to the last base
+    add("si_ends", "short_imperfect", u8 * 5 + _flank(r, 40, "T", u8) + "AAAA" + "CAGT" * 7 + _flank(r, 35, u9, "C")
+        + u9 * 5)
+    add("si_ends_b", "short_imperfect", v9 * 4 + _flank(r, 50, v8, v9) + v8 * 4)
+    add("si_short8", "short_imperfect", "ACACACAC")
+    add("si_short7", "short_imperfect", "ACGACGA")
+    add("si_one", "short_imperfect", "A")
+    # arrays across text positions 63/64 and 127/128: n (with the sentinel) just over 64 and 128
+    add("si_n66", "short_imperfect", _flank(r, 41, u8) + u8 * 3)
+    add("si_n67", "short_imperfect", _flank(r, 38, u9) + u9 * 3 + "T")
+    add("si_n130", "short_imperfect", _flank(r, 50, u8) + u8 * 3 + _flank(r, 31, v8, u8) + v8 * 3)
+    add("si_n131", "short_imperfect", _flank(r, 40, u9) + u9 * 3 + _flank(r, 36, v9, u9) + v9 * 3)
+    add("si_dense_R", "short_imperfect", _dense_unbinned())
+
+    # ---- simple period scan: the reference walks only the periods around the array's (it
+    # needs 8 to 25 s per text for all of 1..200, too close to its 30 s stop)
+    for p in SIMPLE_EDGE_PERIODS:
+        for sub in (False, True):
+            add(f"simple_p{p}_{'sub' if sub else 'exact'}", "simple",
+                _period_text(p, sub, 4 if p <= 129 else 3, 40, SIMPLE_EDGE_SEEDS.get(p, 1000 + p)),
+                min_period=p - 2, max_period=p + 2)
+    for p in (65, 100):     # 1001..3000 bases: max_p = 100
+        for sub in (False, True):
+            add(f"simple_n1k_p{p}_{'sub' if sub else 'exact'}", "simple", _period_text(p, sub, 4, 400, 2000 + p),
+                min_period=p - 2, max_period=p + 2)
+    # two copies + 6/7 of one: accepted only through the partial copy (effective copies 3)
+    u = rnd(70)
+    add("simple_partial_p70", "simple", rnd(40) + u * 2 + u[:60] + rnd(40), min_period=66, max_period=74)
+    u = rnd(60)
+    for name, syms in (("simple_syms10", MANY_SYMBOLS), ("simple_syms6", MANY_SYMBOLS[:6])):
+        arr = "".join(u[:5] + syms[c % len(syms)] + u[6:] for c in range(10))
+        add(name, "simple", rnd(40) + arr + rnd(40), min_period=56, max_period=64)
+    # arrays from position 0 and up to the last base, with partial copies cut by either end
+    u, v, w = rnd(70), rnd(30), rnd(130)
+    add("simple_ends", "simple", u * 3 + rnd(50) + v * 4 + v[:11], min_period=28, max_period=72)
+    add("simple_ends_partial", "simple", u[-33:] + u * 3 + u[:41], min_period=66, max_period=74)
+    add("simple_ends_p130", "simple", w[-50:] + w * 3 + w[:64], min_period=126, max_period=134)
+
+    # ---- Tier 1
+    unit9 = "ACGTTGCAG"
+    for L in range(1, 10):
+        for n in sorted({1, 2, L, 2 * L, 3 * L, 3 * L + 1}):
+            add(f"t1_L{L}_n{n}", "tier1", (unit9[:L] * 4)[:n])
+    add("t1_N_inside", "tier1", "ACGACGACG" + "N" + "ACGACGACGACG")
+    add("t1_AN", "tier1", "GT" + "AN" * 8 + "TG")
+    add("t1_A9", "tier1", "GT" + "A" * 9 + "TG")
+    add("t1_A10", "tier1", "GT" + "A" * 10 + "TG")
+    add("t1_AAC3", "tier1", "GT" + "AAC" * 3 + "TG")
+    add("t1_AAC4", "tier1", "GT" + "AAC" * 4 + "TG")
+    add("t1_at_end", "tier1", "GTCA" + "ACG" * 4)
+    add("t1_iupac", "tier1", "ACRACRACRACR" + "GT" + "acgacgacgacg" + "CATCATCATCAT")
+
+    # ---- LCP plateaus
+    u20, w20 = rnd(20), rnd(20)
+    add("pl_start", "lcp_plateaus", u20 * 6 + rnd(90))
+    add("pl_middle", "lcp_plateaus", rnd(70) + u20 * 6 + rnd(70))
+    add("pl_end", "lcp_plateaus", rnd(90) + u20 * 6)
+    u5 = "CAGTT"
+    add("pl_maxp5", "lcp_plateaus", rnd(50) + u5 * 12 + rnd(50), max_period=5)
+    add("pl_maxp19", "lcp_plateaus", rnd(40) + rnd(19) * 6 + rnd(40) + u20 * 6, max_period=19)
+    add("pl_minp21", "lcp_plateaus", rnd(40) + rnd(21) * 6 + rnd(40) + u20 * 6, min_period=21)
+    add("pl_minp30", "lcp_plateaus", rnd(40) + rnd(28) * 3 + rnd(40), min_period=30)           # max LCP 56
+    add("pl_minp30_no_runs", "lcp_plateaus", rnd(40) + u5 * 5 + rnd(40), min_period=30)        # max LCP < 30
+    add("pl_two_arrays", "lcp_plateaus", rnd(30) + u20 * 4 + rnd(45) + w20 * 5 + rnd(30) + u20 * 4 + rnd(20))
+    add("pl_all_A", "lcp_plateaus", "A" * 100)
+    add("pl_n2", "lcp_plateaus", "A")
+    for n in (255, 256, 257):                      # text bytes with the sentinel: the 256-thread block edge
+        add(f"pl_n{n}", "lcp_plateaus", rnd(n - 1 - 80) + u20 * 4)
+    return cases
+
+
+def _run_library_edge(ref, name, case):
+    """The reference's records of one case, or the exception's name if it raises."""
+    seq, kw = case["seq"], case["params"]
+    finder = case["finder"]
+    core = ref.BWTCore(seq + "$", 32)
+    with contextlib.redirect_stdout(io.StringIO()):
+        if finder == "tier1":
+            return ref.Tier1STRFinder(core.text_arr, 9, False).find_strs(name)
+        f = ref.Tier2LCPFinder(core, **kw)
+        seen = {tuple(x) for x in case["tier1_seen"]}
+        if finder == "short_imperfect":
+            return f.find_short_imperfect_repeats(name, seen)
+        if finder == "lcp_plateaus":
+            return f._detect_lcp_plateaus(f._compute_lcp_array(), name)
+        return f.find_long_repeats(name, seen)
+
+
+def cmd_library_edges(a):
+    """The library finders on the input families the other goldens leave out
+    (N / IUPAC / other bytes in short imperfect arrays, a side list past its
+    first capacity, periods 63..200 of the simple scan, columns of up to 10
+    symbols, arrays at either end of the text, tiny Tier 1 texts, plateau
+    thresholds other than 20) -> library_edges.json.  Each case names the one
+    finder it targets.  `seconds` is rounded up to whole seconds, so a quiet
+    machine regenerates the file byte for byte; simple-scan cases must stay far
+    below the reference's 30 s wall-clock stop (asserted at 10 s)."""
+    import math
+    ref = ref_module()
+    out = {}
+    for name, case in _library_edge_cases().items():
+        t0 = time.time()
+        try:
+            recs = [_rec_json(r) for r in _run_library_edge(ref, name, case)]
+            if case["finder"] == "lcp_plateaus":   # the fields a plateau record sets; the rest are defaults
+                recs = [{k: d[k] for k in PLATEAU_KEYS} for d in recs]
+            err = None
+        except Exception as e:           # recorded: neither side is called on this input
+            recs, err = [], type(e).__name__
+        dt = time.time() - t0
+        if case["finder"] == "simple":
+            assert dt < 10.0, f"{name}: {dt:.1f} s -- too close to the reference's 30 s stop"
+        out[name] = dict(case, records=recs, raises=err, seconds=int(math.ceil(dt)))
+        print(name, len(case["seq"]), len(recs), err, round(dt, 1), flush=True)
+    with open(os.path.join(HERE, "library_edges.json"), "w") as f:
+        json.dump(out, f, indent=0)
+
+
 # ------------------------------------------------------------ edge inputs
 def _edge_inputs():
     """Input edge cases of SURVEY.md §7.3: natural-key
@@ -901,6 +1148,7 @@ def main():
     sp.add_parser("index_rates")
     sp.add_parser("motif")
     sp.add_parser("library")
+    sp.add_parser("library_edges")
     sp.add_parser("tier3")
     sp.add_parser("simple")
     sp.add_parser("edge")
@@ -921,7 +1169,7 @@ def main():
     p.add_argument("--save-out", action="store_true")
     a = ap.parse_args()
     dict(fixtures=cmd_fixtures, rawhits=cmd_rawhits, index=cmd_index, index_rates=cmd_index_rates, motif=cmd_motif,
-         hybrid=cmd_hybrid, homopolymer=cmd_homopolymer, library=cmd_library, tier3=cmd_tier3, simple=cmd_simple, edge=cmd_edge)[a.cmd](a)
+         hybrid=cmd_hybrid, homopolymer=cmd_homopolymer, library=cmd_library, library_edges=cmd_library_edges, tier3=cmd_tier3, simple=cmd_simple, edge=cmd_edge)[a.cmd](a)
 
 
 if __name__ == "__main__":
