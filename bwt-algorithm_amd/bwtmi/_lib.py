@@ -58,6 +58,9 @@ _SIGS = {
                                     C.POINTER(C.POINTER(Hit)), C.POINTER(C.c_int64)]),
     "bwtmi_screen_hits": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "bwtmi_radix_sort": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "bwtmi_exclusive_scan": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int64, C.c_int32,
+                                       C.c_int32, C.c_int64]),
     "bwtmi_index_build": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(_P)]),
     "bwtmi_index_free": (C.c_int, [_P]),
     "bwtmi_index_size": (C.c_int64, [_P]),
@@ -328,6 +331,43 @@ def screen_hits(h, hits, text_len: int, min_copies: int = 3, drop: bool = False,
         return rows[:n.value * 4].reshape(-1, 4).copy()
     finally:
         lib().bwtmi_free(out)
+
+
+# bwtmi_radix_sort kinds: name -> (code, key dtype, value dtype or None)
+SORT_KINDS = {"k64v64": (0, "<u8", "<u8"), "k64v32": (1, "<u8", "<u4"), "k64": (2, "<u8", None),
+              "k32v32": (3, "<u4", "<u4"), "k16v32": (4, "<u2", "<u4"), "pass_k32": (5, "<u4", "<u4")}
+SCAN_KINDS = {"u32": (0, "<u4"), "i64": (1, "<i8")}
+
+
+def radix_sort(h, kind: str, keys, vals, bit0: int, bit1: int, skew: int = 0):
+    """The device radix sort (bwtmi_radix_sort) of `kind` (SORT_KINDS) on copies of
+    keys / vals by the key bits [bit0, bit1): (sorted keys, their values or None).
+    pass_k32: one pass by the digit at bit0."""
+    import numpy as np
+    code, kt, vt = SORT_KINDS[kind]
+    k = np.array(keys, dtype=kt).reshape(-1)
+    v = np.array(vals, dtype=vt).reshape(-1) if vt else None
+    assert v is None or v.size == k.size
+    check(lib().bwtmi_radix_sort(h, code, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p) if vt else None,
+                                 k.size, int(bit0), int(bit1), int(skew)))
+    return k, v
+
+
+def exclusive_scan(h, kind: str, a, n: Optional[int] = None, rows: int = 1, stride: int = 0, skew: int = 0,
+                   in_place: bool = False, epoch: int = 0, out=None):
+    """The device exclusive scan (bwtmi_exclusive_scan) of `kind` (SCAN_KINDS) over
+    `rows` rows of n elements of a, `stride` apart (one row: all of a).  Returns
+    the output array; out of place it starts as a copy of `out` (zeros if None)."""
+    import numpy as np
+    code, dt = SCAN_KINDS[kind]
+    a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+    n = a.size if n is None else int(n)
+    assert a.size == (rows - 1) * stride + n
+    o = np.zeros_like(a) if out is None else np.array(out, dtype=dt).reshape(-1)
+    assert o.size == a.size
+    check(lib().bwtmi_exclusive_scan(h, code, a.ctypes.data_as(C.c_void_p), o.ctypes.data_as(C.c_void_p), n, int(rows),
+                                     int(stride), int(skew), int(bool(in_place)), int(epoch)))
+    return o
 
 
 def host_info() -> dict:

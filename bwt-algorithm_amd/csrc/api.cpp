@@ -145,6 +145,7 @@ using namespace bwtmi;
 
 struct bwtmi_ctx {
     Ctx c;
+    DBuf prim[4];   // the caller's arrays of bwtmi_radix_sort / bwtmi_exclusive_scan (no slot of c: the primitives own those)
 };
 struct bwtmi_index {
     DeviceIndex *d = nullptr;
@@ -190,6 +191,44 @@ void write_start(bwtmi_job *job, int fmt, const char *path) {
     f->render_done();
     job->wr = std::move(w);
 }
+// A caller's array of n elements of `es` bytes on the device (bwtmi_radix_sort,
+// bwtmi_exclusive_scan): it starts kPrimPad + skew elements into an allocation
+// of n + 3 * kPrimPad elements filled with kPrimFill, so skew = 0 is 16-byte
+// aligned, another skew is not (for some element sizes), and the elements on
+// both sides are guards that a primitive writing outside [0, n) changes.
+constexpr int kPrimPad = 16;
+constexpr int kPrimFill = 0xA5;
+struct PrimArr {
+    DBuf &buf;
+    size_t es;
+    int64_t n;
+    int skew;
+    std::vector<uint8_t> img;   // the whole allocation, downloaded
+    size_t total() const { return (size_t)(n + 3 * kPrimPad) * es; }
+    size_t first() const { return (size_t)(kPrimPad + skew) * es; }
+    size_t bytes() const { return (size_t)n * es; }
+    template <class T> T *dev() const { return reinterpret_cast<T *>(buf.as<uint8_t>() + first()); }
+    void upload(Ctx &c, const void *src) {
+        buf.ensure(total());
+        HIPCHECK(hipMemsetAsync(buf.p, kPrimFill, total(), c.stream));
+        if (src && n) HIPCHECK(hipMemcpyAsync(dev<uint8_t>(), src, bytes(), hipMemcpyHostToDevice, c.stream));
+    }
+    void download(Ctx &c) {
+        img.resize(total());
+        HIPCHECK(hipMemcpyAsync(img.data(), buf.p, total(), hipMemcpyDeviceToHost, c.stream));
+    }
+    const uint8_t *data() const { return img.data() + first(); }
+    // after download and a stream wait: the guards still hold the fill
+    void check_guards(const char *what) const {
+        for (size_t i = 0; i < img.size(); i = i + 1 == first() ? first() + bytes() : i + 1)
+            if (img[i] != kPrimFill)
+                fail(BWTMI_E_STATE, "%s: byte %lld outside the array's %lld bytes was written", what,
+                     (long long)i - (long long)first(), (long long)bytes());
+    }
+    void check_same(const void *src, const char *what) const {
+        if (n && std::memcmp(data(), src, bytes()) != 0) fail(BWTMI_E_STATE, "%s: the input array changed", what);
+    }
+};
 }  // namespace
 
 // readers of contig bytes join a deferred host pass first (bwtmi_job_load_fasta_dev)
@@ -351,6 +390,7 @@ int bwtmi_close(bwtmi_ctx *ctx) {
         ctx_join(ctx->c);   // a background error dies with the context
         ctx->c.activate();
         ctx_release(ctx->c);
+        for (auto &b : ctx->prim) b.release();
         delete ctx;
     });
 }
@@ -474,6 +514,106 @@ int bwtmi_screen_hits(bwtmi_ctx *ctx, const bwtmi_hit *hits, int64_t n, int64_t 
         }
         *nout = (int64_t)rows.size() / 4;
         *out = malloc_copy(rows);
+    });
+}
+
+// ------------------------------------------------------------ primitives
+// the radix sorts of radix.hip on a caller's arrays (tests, embedders): the
+// arrays go to buffers of the entry's own, the primitive runs as its callers
+// run it, the results come back into the caller's arrays
+int bwtmi_radix_sort(bwtmi_ctx *ctx, int32_t kind, void *keys, void *vals, int64_t n, int32_t bit0, int32_t bit1,
+                     int32_t skew) {
+    return guard([&] {
+        CHECK_ARG(ctx, "null context");
+        CHECK_ARG(kind >= BWTMI_SORT_K64V64 && kind <= BWTMI_SORT_PASS_K32, "unknown sort kind");
+        const size_t kb = kind <= BWTMI_SORT_K64 ? 8 : kind == BWTMI_SORT_K16V32 ? 2 : 4;
+        const size_t vb = kind == BWTMI_SORT_K64V64 ? 8 : kind == BWTMI_SORT_K64 ? 0 : 4;
+        CHECK_ARG(n >= 0 && n < (int64_t{1} << 32), "n outside 0 .. 2^32 - 1");
+        CHECK_ARG(n == 0 || (keys && (vals || !vb)), "null array");
+        CHECK_ARG(bit0 >= 0 && bit1 <= (int32_t)(8 * kb) && bit0 < bit1 && (bit1 - bit0) % 8 == 0,
+                  "need 0 <= bit0 < bit1 <= the key width and a whole number of 8-bit digits");
+        CHECK_ARG(kind != BWTMI_SORT_PASS_K32 || bit1 == bit0 + 8, "one pass sorts one digit: bit1 = bit0 + 8");
+        CHECK_ARG(skew >= 0 && skew < kPrimPad, "skew outside 0..15");
+        if (n == 0) return;
+        Ctx &c = ctx->c;
+        use(c);
+        PrimArr k{ctx->prim[0], kb, n, skew}, v{ctx->prim[1], vb, vb ? n : 0, skew};
+        k.upload(c, keys);
+        if (vb) v.upload(c, vals);
+        if (kind == BWTMI_SORT_PASS_K32) {
+            PrimArr ko{ctx->prim[2], kb, n, skew}, vo{ctx->prim[3], vb, n, skew};
+            ko.upload(c, nullptr);
+            vo.upload(c, nullptr);
+            radix_pass_k32(c, k.dev<uint32_t>(), v.dev<uint32_t>(), ko.dev<uint32_t>(), vo.dev<uint32_t>(), n, bit0);
+            for (PrimArr *a : {&k, &v, &ko, &vo}) a->download(c);
+            HIPCHECK(hipStreamSynchronize(c.stream));
+            c.kresolve();
+            c.checks_verify("bwtmi_radix_sort");
+            for (PrimArr *a : {&k, &v, &ko, &vo}) a->check_guards("bwtmi_radix_sort");
+            k.check_same(keys, "bwtmi_radix_sort (pass keys)");
+            v.check_same(vals, "bwtmi_radix_sort (pass values)");
+            std::memcpy(keys, ko.data(), ko.bytes());
+            std::memcpy(vals, vo.data(), vo.bytes());
+            return;
+        }
+        switch (kind) {
+        case BWTMI_SORT_K64V64: radix_sort_pairs(c, k.dev<uint64_t>(), v.dev<uint64_t>(), n, bit0, bit1); break;
+        case BWTMI_SORT_K64V32: radix_sort_pairs32(c, k.dev<uint64_t>(), v.dev<uint32_t>(), n, bit0, bit1); break;
+        case BWTMI_SORT_K64: radix_sort_pairs32(c, k.dev<uint64_t>(), nullptr, n, bit0, bit1); break;
+        case BWTMI_SORT_K32V32: radix_sort_pairs_k32(c, k.dev<uint32_t>(), v.dev<uint32_t>(), n, bit0, bit1); break;
+        default: radix_sort_pairs_k16(c, k.dev<uint16_t>(), v.dev<uint32_t>(), n, bit0, bit1); break;
+        }
+        k.download(c);
+        if (vb) v.download(c);
+        HIPCHECK(hipStreamSynchronize(c.stream));
+        c.kresolve();
+        c.checks_verify("bwtmi_radix_sort");
+        k.check_guards("bwtmi_radix_sort");
+        if (vb) v.check_guards("bwtmi_radix_sort");
+        std::memcpy(keys, k.data(), k.bytes());
+        if (vb) std::memcpy(vals, v.data(), v.bytes());
+    });
+}
+
+// the exclusive scans of radix.hip on a caller's array(s)
+int bwtmi_exclusive_scan(bwtmi_ctx *ctx, int32_t kind, const void *in, void *out, int64_t n, int32_t rows,
+                         int64_t stride, int32_t skew, int32_t in_place, int64_t epoch) {
+    return guard([&] {
+        CHECK_ARG(ctx, "null context");
+        CHECK_ARG(kind == BWTMI_SCAN_U32 || kind == BWTMI_SCAN_I64, "unknown scan kind");
+        CHECK_ARG(n >= 0 && n < (int64_t{1} << 32) && rows >= 1 && rows <= 65536 && stride >= 0 &&
+                      stride < (int64_t{1} << 32), "n, rows or stride out of range");
+        CHECK_ARG(kind == BWTMI_SCAN_U32 || rows == 1, "the 64-bit scan takes one row");
+        CHECK_ARG(rows == 1 || stride >= n, "rows overlap: stride < n");
+        CHECK_ARG(n == 0 || (in && out), "null array");
+        CHECK_ARG(skew >= 0 && skew < kPrimPad, "skew outside 0..15");
+        Ctx &c = ctx->c;
+        use(c);   // (joins background work that draws epochs)
+        // the epoch only ever moves forward: a granule of a later epoch than the
+        // next launch's cannot exist, so no stale granule can match
+        CHECK_ARG(epoch == 0 || (epoch > (int64_t)c.lb_epoch && epoch < (int64_t{1} << 30)),
+                  "epoch must be above the context's and below 2^30");
+        if (n == 0) return;
+        if (epoch) c.lb_epoch = (uint32_t)epoch;
+        const size_t es = kind == BWTMI_SCAN_U32 ? 4 : 8;
+        const int64_t total = (int64_t)(rows - 1) * stride + n;
+        PrimArr a{ctx->prim[0], es, total, skew}, b{ctx->prim[1], es, total, skew};
+        a.upload(c, in);
+        if (!in_place) b.upload(c, out);   // what the scan does not write stays the caller's
+        PrimArr &o = in_place ? a : b;
+        if (kind == BWTMI_SCAN_I64) exclusive_scan<int64_t>(c, a.dev<int64_t>(), o.dev<int64_t>(), n);
+        else if (rows == 1) exclusive_scan<uint32_t>(c, a.dev<uint32_t>(), o.dev<uint32_t>(), n);
+        else exclusive_scan_rows(c, a.dev<uint32_t>(), o.dev<uint32_t>(), n, rows, stride);
+        a.download(c);
+        if (!in_place) b.download(c);
+        HIPCHECK(hipStreamSynchronize(c.stream));
+        c.kresolve();
+        a.check_guards("bwtmi_exclusive_scan");
+        if (!in_place) {
+            b.check_guards("bwtmi_exclusive_scan");
+            a.check_same(in, "bwtmi_exclusive_scan");
+        }
+        std::memcpy(out, o.data(), o.bytes());
     });
 }
 

@@ -130,6 +130,70 @@ int bwtmi_screen_hits(bwtmi_ctx *ctx, const bwtmi_hit *hits, int64_t n, int64_t 
                       int32_t min_copies, int32_t drop, int64_t maxlen,
                       int64_t **out, int64_t *nout);
 
+/* ------------------------------------------------------------ device primitives
+ * The radix sort and the exclusive scans every device stage is built on
+ * (radix.hip), run on a caller's host arrays (tests, embedders): the arrays are
+ * copied to device buffers of the entry's own, the primitive runs on the
+ * context's stream exactly as the library's stages call it, and the results are
+ * copied back.  Not in the reference.
+ *
+ * bwtmi_radix_sort: the stable LSD sort of n keys (and their values) by the
+ * key bits [bit0, bit1), 8 bits per pass, in place in the caller's arrays.
+ *   kind   K64V64  uint64 keys, uint64 values       K32V32    uint32 / uint32
+ *          K64V32  uint64 keys, uint32 values       K16V32    uint16 / uint32
+ *          K64     uint64 keys alone (vals is not read and may be NULL)
+ *          PASS_K32  one out-of-place pass over uint32 keys and values by the
+ *                  digit at bit0 (bit1 = bit0 + 8): the pass's outputs come back
+ *                  in keys / vals, and the call fails with BWTMI_E_STATE if the
+ *                  pass changed its inputs on the device.
+ *   skew   0..15: the device arrays start that many elements past a 16-byte
+ *          aligned address (0: the histogram's 16-byte loads; otherwise, unless
+ *          skew elements are a multiple of 16 bytes, its scalar loads).
+ *   stable pairs of equal digits keep their order: the result is
+ *          keys[order], vals[order] with order = the stable argsort of
+ *          (keys >> bit0) & (2^(bit1 - bit0) - 1); bits outside the range ride along.
+ *   errors BWTMI_E_ARG before anything reaches the device, the arrays
+ *          untouched: an unknown kind, n < 0 or n >= 2^32, a null array with
+ *          n > 0, bit0 < 0, bit1 above the key width, bit0 >= bit1, a range that
+ *          is not a whole number of 8-bit digits (the library's own callers get
+ *          such a range rounded up; this entry refuses it), skew outside 0..15.
+ *          BWTMI_E_STATE: a device check (BWTMI_DEVICE_CHECKS) fired, or bytes
+ *          next to the device arrays were written.  n = 0 is legal. */
+#define BWTMI_SORT_K64V64 0
+#define BWTMI_SORT_K64V32 1
+#define BWTMI_SORT_K64 2
+#define BWTMI_SORT_K32V32 3
+#define BWTMI_SORT_K16V32 4
+#define BWTMI_SORT_PASS_K32 5
+int bwtmi_radix_sort(bwtmi_ctx *ctx, int32_t kind, void *keys, void *vals, int64_t n, int32_t bit0,
+                     int32_t bit1, int32_t skew);
+/* bwtmi_exclusive_scan: out[r * stride + i] = in[r * stride] + ... + in[r * stride + i - 1]
+ * for each of `rows` rows of n elements, `stride` elements apart (rows = 1:
+ * stride is not read).  in and out hold (rows - 1) * stride + n elements.
+ *   kind     U32: uint32 sums mod 2^32, any number of rows (the single-pass
+ *            look-back scan).  I64: int64 sums, rows = 1 (the three-launch scan).
+ *   in_place != 0: the scan runs with out == in on the device.  Otherwise the
+ *            device output array starts as a copy of the caller's `out`, so the
+ *            elements between rows come back as they were, and the call fails
+ *            with BWTMI_E_STATE if the scan changed its input.
+ *   skew     0..15: as above, for the first row's base on the device.
+ *   epoch    0: nothing.  Otherwise the context's look-back epoch (the tag that
+ *            tells one launch's published tile sums from an earlier launch's,
+ *            drawn per launch, wrapping at 2^30 with the sums cleared) is set to
+ *            this value before the scan, so a test can reach the wrap.  Accepted
+ *            only when it is above the context's current epoch and below 2^30:
+ *            the epoch never moves backwards, because an epoch used twice
+ *            without the clear between could match a stale sum.
+ *   errors   BWTMI_E_ARG before anything reaches the device, `out` untouched:
+ *            an unknown kind, n, rows - 1 or stride negative (or n, stride >=
+ *            2^32, rows > 65536), a null array with n > 0, rows > 1 with I64 or
+ *            with stride < n, skew outside 0..15, an epoch not accepted.
+ *            n = 0 is legal. */
+#define BWTMI_SCAN_U32 0
+#define BWTMI_SCAN_I64 1
+int bwtmi_exclusive_scan(bwtmi_ctx *ctx, int32_t kind, const void *in, void *out, int64_t n, int32_t rows,
+                         int64_t stride, int32_t skew, int32_t in_place, int64_t epoch);
+
 /* ------------------------------------------------------------ FM index
  * Replaces BWTCore.__init__ (bwt.py:106-136): suffix array (212-264), BWT
  * (266-274), C table (276-286), Occ checkpoints (288-326), sampled SA
