@@ -255,6 +255,9 @@ struct Ctx {
         c.kend();                                                              \
     } while (0)
 
+// grid size of a launch of one thread per element
+inline unsigned blocks(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
+
 // The scan's host reads (candidate counts, key widths, hit counts) wait on the
 // stream by polling: a blocking wait (hipDeviceScheduleBlockingSync, kept for
 // the long waits behind host work) sleeps the thread, and its wake-up delays
@@ -377,7 +380,29 @@ bool sa_small_device(Ctx &c, const uint8_t *t, int64_t n, uint32_t *SA, uint8_t 
 // for DMA (api.cpp); the block stays registered while it is cached
 bool ensure_pinned(const void *base, const void *p, size_t n);
 
-struct DeviceIndex;
+struct DeviceIndex {
+    int64_t n = 0;
+    int32_t sa_sample = 32, occ_sample = 128;
+    int sigma = 0;
+    uint8_t code_of[256];        // byte -> occ row (valid when totals > 0)
+    int64_t totals[256], C[256];
+    DBuf text;                   // copy of the text (n + pad)
+    DBuf sa;                     // int32[n]
+    DBuf bwt;                    // uint8[n + pad]
+    DBuf occ;                    // int32[sigma][occ_len]
+    DBuf sampled;                // int32[ceil(n/s)]
+    DBuf kmer_off;               // int64[65537]
+    DBuf kmer_pos;               // int32[count]
+    int64_t kmer_count = 0;
+    bool has_kmer = false;
+    int64_t occ_len = 0, sampled_len = 0;
+    // ACGT* '$' texts: packed rank structure, one 32-byte block per 64 BWT rows:
+    // uint32 count[4] of A C G T before the block, then the rows' 2-bit codes
+    // as two bit planes (row 64b + k at bit k; '$' stored as A, dollar_row)
+    DBuf fm2;
+    bool has_fm2 = false;
+    int64_t dollar_row = -1;
+};
 // d_text: device text incl. sentinel, n bytes (padded by >= 64 bytes)
 DeviceIndex *index_build_device(Ctx &c, const uint8_t *d_text, int64_t n, int32_t sa_sample,
                                 int32_t occ_sample, uint32_t flags, DeviceIndex *reuse = nullptr);
@@ -413,18 +438,19 @@ void short_imperfect_device(Ctx &c, DeviceIndex *ix, const LibParams &p, const s
 // Tier1STRFinder.find_strs (bwt.py:1426-1538) over text t (host) / d_text (device copy, n bytes)
 void tier1_device(Ctx &c, const uint8_t *d_text, const uint8_t *t, int64_t n, int32_t max_motif_length,
                   int32_t chrom, RecVec &out);
+// Tier2LCPFinder.find_long_repeats -> _find_repeats_simple (bwt.py:2097-2106, 2177-2498)
+void simple_scan_device(Ctx &c, DeviceIndex *ix, const LibParams &p, const std::vector<int64_t> &seen_pairs,
+                        int32_t chrom, RecVec &out);
+// Tier3LongReadFinder.find_very_long_repeats (bwt.py:2837-3036) of `reads` (concatenated,
+// read_off[nreads + 1]) against the index; consolidated records with chrom = `chrom`
+void tier3_device(Ctx &c, DeviceIndex *ix, const uint8_t *reads, const int64_t *read_off, int64_t nreads,
+                  int32_t chrom, RecVec &out);
+
+// ----- queries over a built index (search.hip; contracts of the batched ones in bwtmi.h)
 void index_backward_search(Ctx &c, DeviceIndex *, const uint8_t *pats, const int64_t *off, int64_t npat,
                            int64_t *sp_ep);
 void index_sa_rows(Ctx &c, const DeviceIndex *, const int64_t *rows, int64_t k, int64_t *out);
-// exact backward search of np pieces d_pats[d_off[p], d_off[p + 1]) (device arrays, plen bytes
-// in all) with the results left on the device: first SA row and width (0 = absent) per piece
-void index_seed_search_device(Ctx &c, DeviceIndex *, const uint8_t *d_pats, const int64_t *d_off, int64_t np,
-                              int64_t plen, int64_t *d_row0, int64_t *d_width);
-
-// ----- batched locate with mismatches on both strands (locate.hip; contract in bwtmi.h)
-constexpr int kLocMaxMismatch = 3;
-constexpr int64_t kLocMaxPattern = 1024;
-constexpr int64_t kLocDefaultCap = int64_t{1} << 27;
+// batched locate with mismatches on both strands
 struct LocateResult {
     std::vector<int64_t> hit_off, pos;   // npat + 1 offsets; positions
     std::vector<uint8_t> mm, strand;     // mismatches; 0 = '+', 1 = '-'
@@ -432,37 +458,7 @@ struct LocateResult {
 };
 void index_locate_batch(Ctx &c, DeviceIndex *ix, const uint8_t *pats, const int64_t *off, int64_t npat,
                         int32_t max_mismatch, bool both_strands, int64_t max_candidates, LocateResult &out);
-
-// ----- batched SMEM seeding of reads (smem.hip; contract in bwtmi.h)
-constexpr int64_t kSmemMaxQuery = 1024;
-constexpr int64_t kSmemDefaultMaxOcc = 1024;
-// one searched string (a query, or its reverse complement): its bytes start at
-// qoff of the uploaded bytes, which is also its first lane
-struct SmemStr {
-    int64_t qoff;
-    int32_t query;
-    uint32_t info;   // m (11 bits) | strand << 11
-};
-static_assert(kSmemMaxQuery <= 1024, "SmemStr::info field widths");
-// Lane g is byte g of the strings laid back to back: its string (str: ns
-// entries ascending by qoff, str[0].qoff = 0) and its end e in 1..m.  A '+'
-// string takes its ends ascending, a '-' string descending, so that lane order
-// is (query, strand, qstart) order.
-__device__ __forceinline__ int smem_lane(const SmemStr *__restrict__ str, int64_t ns, int64_t g, SmemStr &s) {
-    int64_t lo = 0, hi = ns;   // str[lo].qoff <= g < str[hi].qoff
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (str[mid].qoff <= g) lo = mid;
-        else hi = mid;
-    }
-    s = str[lo];
-    const int m = (int)(s.info & 2047u), t = (int)(g - s.qoff);
-    return (s.info >> 11) & 1u ? m - t : t + 1;
-}
-// matching statistics of every (string, end) lane, left on the device (index.hip);
-// max_steps = the sum of the lanes' ends, the bound of the rank steps (byte model)
-void index_smem_ms_device(Ctx &c, DeviceIndex *, const uint8_t *d_q, const SmemStr *d_str, int64_t ns, int64_t nl,
-                          double max_steps, int32_t *d_ell, int64_t *d_row0, int64_t *d_width);
+// batched SMEM seeding of reads
 struct SmemResult {
     std::vector<int64_t> smem_off;         // nq + 1
     std::vector<int32_t> qstart, qend;     // per SMEM
@@ -473,12 +469,5 @@ struct SmemResult {
 };
 void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq, int32_t min_len,
                       bool both_strands, int64_t max_occ, int64_t max_positions, SmemResult &out);
-// Tier2LCPFinder.find_long_repeats -> _find_repeats_simple (bwt.py:2097-2106, 2177-2498)
-void simple_scan_device(Ctx &c, DeviceIndex *ix, const LibParams &p, const std::vector<int64_t> &seen_pairs,
-                        int32_t chrom, RecVec &out);
-// Tier3LongReadFinder.find_very_long_repeats (bwt.py:2837-3036) of `reads` (concatenated,
-// read_off[nreads + 1]) against the index; consolidated records with chrom = `chrom`
-void tier3_device(Ctx &c, DeviceIndex *ix, const uint8_t *reads, const int64_t *read_off, int64_t nreads,
-                  int32_t chrom, RecVec &out);
 
 }  // namespace bwtmi

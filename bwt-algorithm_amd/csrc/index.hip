@@ -1,5 +1,6 @@
 // index.hip -- FM-index construction on gfx950 (replaces BWTCore.__init__,
-// bwt.py:106-136) plus the library queries built on it.
+// bwt.py:106-136), its getters and the LCP array; search.hip reads what is
+// built here.
 //
 // Suffix array (bwt.py:212-264).  The reference sorts suffixes of seq+'$' by
 // byte value with "end of text" smallest; '$' unique makes the order total.
@@ -12,7 +13,7 @@
 //            singletons are dropped (h doubles each round)
 // BWT/C/Occ/sampled SA are single streaming kernels; the 8-mer hash is a
 // stable 16-bit radix sort of (window code, position) pairs; LCP is chunked
-// Kasai; backward search runs one pattern per lane.
+// Kasai.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,30 +24,6 @@
 #include "device.h"
 
 namespace bwtmi {
-
-struct DeviceIndex {
-    int64_t n = 0;
-    int32_t sa_sample = 32, occ_sample = 128;
-    int sigma = 0;
-    uint8_t code_of[256];        // byte -> occ row (valid when totals > 0)
-    int64_t totals[256], C[256];
-    DBuf text;                   // copy of the text (n + pad)
-    DBuf sa;                     // int32[n]
-    DBuf bwt;                    // uint8[n + pad]
-    DBuf occ;                    // int32[sigma][occ_len]
-    DBuf sampled;                // int32[ceil(n/s)]
-    DBuf kmer_off;               // int64[65537]
-    DBuf kmer_pos;               // int32[count]
-    int64_t kmer_count = 0;
-    bool has_kmer = false;
-    int64_t occ_len = 0, sampled_len = 0;
-    // ACGT* '$' texts: packed rank structure, one 32-byte block per 64 BWT rows:
-    // uint32 count[4] of A C G T before the block, then the rows' 2-bit codes
-    // as two bit planes (row 64b + k at bit k; '$' stored as A, dollar_row)
-    DBuf fm2;
-    bool has_fm2 = false;
-    int64_t dollar_row = -1;
-};
 
 namespace {
 
@@ -444,229 +421,6 @@ __global__ __launch_bounds__(256) void k_fm2_counts(const uint32_t *__restrict__
     for (int q = 0; q < 4; ++q) fm2u32[8 * b + q] = cnt4[(int64_t)q * (nb + 1) + b];
 }
 
-struct FM2View {
-    const uint4 *blk;      // 2 x uint4 per block
-    int64_t C[5], tot[5];  // codes A C G T $
-    int64_t n, dollar;
-};
-
-// occurrences of code c (0-3; 4 = '$') in bwt[0, i), 0 <= i <= n
-__device__ __forceinline__ int64_t rank2(const FM2View &f, int c, int64_t i) {
-    if (c == 4) return f.dollar < i ? 1 : 0;
-    const int64_t b = i >> 6;
-    const int r = (int)(i & 63);
-    const uint4 h = f.blk[2 * b], p = f.blk[2 * b + 1];
-    const uint32_t cnt = c == 0 ? h.x : c == 1 ? h.y : c == 2 ? h.z : h.w;
-    const uint64_t lo = ((uint64_t)p.y << 32) | p.x, hi = ((uint64_t)p.w << 32) | p.z;
-    const uint64_t m = ((c & 1) ? lo : ~lo) & ((c & 2) ? hi : ~hi);
-    const uint64_t below = r ? (~0ull >> (64 - r)) : 0ull;
-    int64_t x = (int64_t)cnt + __popcll(m & below);
-    if (c == 0 && f.dollar >= 64 * b && f.dollar < i) --x;   // the '$' row reads as A in the planes
-    return x;
-}
-
-__device__ __forceinline__ int code5(uint8_t ch) {
-    switch (ch) {
-        case 'A': return 0;
-        case 'C': return 1;
-        case 'G': return 2;
-        case 'T': return 3;
-        case '$': return 4;
-        default: return -1;
-    }
-}
-
-// one step of the backward search over the packed rank (two 32-byte block
-// loads and two popcounts): [sp, ep] of a string X -> [sp, ep] of ch X; false
-// (sp, ep as they were) when ch X does not occur
-__device__ __forceinline__ bool bstep2(const FM2View &f, uint8_t ch, int64_t &sp, int64_t &ep) {
-    const int c = code5(ch);
-    if (c < 0 || f.tot[c] == 0) return false;
-    const int64_t s = f.C[c] + rank2(f, c, sp), e = f.C[c] + rank2(f, c, ep + 1) - 1;
-    if (s > e) return false;
-    sp = s;
-    ep = e;
-    return true;
-}
-
-// backward search over the packed rank, one pattern per lane: the lane's search of pats[a, b)
-// (shared by k_bsearch2 and the locate seed search, k_loc_seed2)
-__device__ __forceinline__ void bsearch2_lane(const FM2View &f, const uint8_t *__restrict__ pats, int64_t a, int64_t b,
-                                              int64_t &sp, int64_t &ep) {
-    sp = ep = -1;
-    if (b == a) {
-        sp = 0;
-        ep = f.n - 1;
-        return;
-    }
-    const int c = code5(pats[b - 1]);
-    if (c >= 0 && f.tot[c] > 0) {
-        sp = f.C[c];
-        ep = sp + f.tot[c] - 1;
-        for (int64_t i = b - 2; i >= a; --i)
-            if (!bstep2(f, pats[i], sp, ep)) { sp = ep = -1; break; }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_bsearch2(FM2View f, const uint8_t *__restrict__ pats,
-                                                  const int64_t *__restrict__ off, int64_t np,
-                                                  int64_t *__restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= np) return;
-    int64_t sp, ep;
-    bsearch2_lane(f, pats, off[p], off[p + 1], sp, ep);
-    out[2 * p] = sp;
-    out[2 * p + 1] = ep;
-}
-
-// the locate seed search: the interval's first row and its width (0 = no
-// occurrence) of every piece, left on the device
-__global__ __launch_bounds__(256) void k_loc_seed2(FM2View f, const uint8_t *__restrict__ pats,
-                                                   const int64_t *__restrict__ off, int64_t np,
-                                                   int64_t *__restrict__ row0, int64_t *__restrict__ width) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= np) return;
-    int64_t sp, ep;
-    bsearch2_lane(f, pats, off[p], off[p + 1], sp, ep);
-    row0[p] = sp < 0 ? 0 : sp;
-    width[p] = sp < 0 ? 0 : ep - sp + 1;
-}
-
-// ---- backward search (bwt.py:335-389), one pattern per lane
-struct FMView {
-    const uint8_t *bwt;
-    const int32_t *occ;
-    const int64_t *C;
-    const int64_t *tot;
-    const uint8_t *row;
-    int64_t n, olen;
-    int32_t k;
-};
-
-__device__ int64_t d_rank(const FMView &f, uint8_t c, int64_t pos) {
-    if (pos <= 0) return 0;
-    if (pos > f.n) pos = f.n;
-    const int64_t ci = pos / f.k, cpos = ci * f.k;
-    int64_t base = f.occ[(int64_t)f.row[c] * f.olen + ci];
-    for (int64_t i = cpos; i < pos; ++i) base += f.bwt[i] == c;
-    return base;
-}
-
-// one step over the byte Occ (bstep2's contract)
-__device__ __forceinline__ bool bstep(const FMView &f, uint8_t c, int64_t &sp, int64_t &ep) {
-    if (f.tot[c] == 0) return false;
-    const int64_t s = f.C[c] + d_rank(f, c, sp), e = f.C[c] + d_rank(f, c, ep + 1) - 1;
-    if (s > e) return false;
-    sp = s;
-    ep = e;
-    return true;
-}
-
-// the lane's search of pats[a, b) (shared by k_bsearch and k_loc_seed)
-__device__ __forceinline__ void bsearch_lane(const FMView &f, const uint8_t *__restrict__ pats, int64_t a, int64_t b,
-                                             int64_t &sp, int64_t &ep) {
-    sp = ep = -1;
-    if (b == a) {
-        sp = 0;
-        ep = f.n - 1;
-        return;
-    }
-    const uint8_t c = pats[b - 1];
-    if (f.tot[c] > 0) {
-        sp = f.C[c];
-        ep = sp + f.tot[c] - 1;
-        for (int64_t i = b - 2; i >= a; --i)
-            if (!bstep(f, pats[i], sp, ep)) { sp = ep = -1; break; }
-    }
-}
-
-__global__ void k_bsearch(FMView f, const uint8_t *__restrict__ pats, const int64_t *__restrict__ off, int64_t np,
-                          int64_t *__restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= np) return;
-    int64_t sp, ep;
-    bsearch_lane(f, pats, off[p], off[p + 1], sp, ep);
-    out[2 * p] = sp;
-    out[2 * p + 1] = ep;
-}
-
-__global__ void k_loc_seed(FMView f, const uint8_t *__restrict__ pats, const int64_t *__restrict__ off, int64_t np,
-                           int64_t *__restrict__ row0, int64_t *__restrict__ width) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= np) return;
-    int64_t sp, ep;
-    bsearch_lane(f, pats, off[p], off[p + 1], sp, ep);
-    row0[p] = sp < 0 ? 0 : sp;
-    width[p] = sp < 0 ? 0 : ep - sp + 1;
-}
-
-// ---- matching statistics of the SMEM search (smem.hip), one lane per
-// (searched string, end e) (smem_lane, device.h).  The lane extends Q[e - 1]
-// leftwards while the interval stays non-empty: ell = l(e), row0 / width =
-// the SA interval of Q[e - l, e) (width 0 when l = 0).  The lanes of a
-// wave are consecutive ends of one string: at step j they read consecutive
-// bytes and their l differ by at most their distance.  The loops end on the
-// lane's own interval only.
-__global__ __launch_bounds__(256) void k_smem_ms2(FM2View f, const uint8_t *__restrict__ q,
-                                                  const SmemStr *__restrict__ str, int64_t ns, int64_t nl,
-                                                  int32_t *__restrict__ ell, int64_t *__restrict__ row0,
-                                                  int64_t *__restrict__ width) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nl) return;
-    SmemStr s;
-    const int e = smem_lane(str, ns, g, s);   // device.h
-    const uint8_t *__restrict__ qq = q + s.qoff;
-    int l = 0;
-    int64_t sp = 0, ep = -1;
-    const int c = code5(qq[e - 1]);
-    if (c >= 0 && f.tot[c] > 0) {
-        sp = f.C[c];
-        ep = sp + f.tot[c] - 1;
-        l = 1;
-        // the text's one '$' is its last byte: '$' X (X not empty) occurs nowhere, and the
-        // step would find it wrapped round the end of the text
-        for (int i = e - 2; i >= 0 && qq[i] != '$' && bstep2(f, qq[i], sp, ep); --i) ++l;
-    }
-    ell[g] = l;
-    row0[g] = sp;
-    width[g] = ep - sp + 1;
-}
-
-__global__ __launch_bounds__(256) void k_smem_ms(FMView f, const uint8_t *__restrict__ text,
-                                                 const uint8_t *__restrict__ q, const SmemStr *__restrict__ str,
-                                                 int64_t ns, int64_t nl, int32_t *__restrict__ ell,
-                                                 int64_t *__restrict__ row0, int64_t *__restrict__ width) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= nl) return;
-    SmemStr s;
-    const int e = smem_lane(str, ns, g, s);   // device.h
-    const uint8_t *__restrict__ qq = q + s.qoff;
-    int l = 0;
-    int64_t sp = 0, ep = -1;
-    const uint8_t c = qq[e - 1], last = text[f.n - 1];
-    if (f.tot[c] > 0) {
-        sp = f.C[c];
-        ep = sp + f.tot[c] - 1;
-        l = 1;
-        for (int i = e - 2; i >= 0; --i) {
-            const uint8_t b = qq[i];
-            int64_t s2 = sp, e2 = ep;
-            if (!bstep(f, b, s2, e2)) break;
-            // the first row of the text's last byte is the suffix made of that byte alone:
-            // 'b X' (X not empty) found there wraps round the end of the text
-            if (b == last && s2 == f.C[b] && ++s2 > e2) break;
-            sp = s2;
-            ep = e2;
-            ++l;
-        }
-    }
-    ell[g] = l;
-    row0[g] = sp;
-    width[g] = ep - sp + 1;
-}
-
-inline unsigned blocks(int64_t n, int b = 256) { return (unsigned)((n + b - 1) / b); }
-
 }  // namespace
 
 // Suffix array of any text by prefix doubling over radix sorts (see the file
@@ -1013,133 +767,6 @@ const int32_t *index_lcp_device(Ctx &c, DeviceIndex *ix) {
     }
     HIPCHECK(hipGetLastError());
     return lcp;
-}
-
-namespace {
-__global__ void k_sa_rows(const uint32_t *__restrict__ sa, const int64_t *__restrict__ rows, int64_t k,
-                          int64_t *__restrict__ out) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < k) out[j] = (int64_t)sa[rows[j]];
-}
-}  // namespace
-
-// SA[rows[j]] for k rows (host arrays; every row < n)
-void index_sa_rows(Ctx &c, const DeviceIndex *ix, const int64_t *rows, int64_t k, int64_t *out) {
-    if (k <= 0) return;
-    for (int64_t j = 0; j < k; ++j)
-        if (rows[j] < 0 || rows[j] >= ix->n) fail(BWTMI_E_ARG, "SA row %lld out of range", (long long)rows[j]);
-    hipStream_t st = c.stream;
-    c.slot[S_MISC0].ensure((size_t)k * 8);
-    c.slot[S_MISC1].ensure((size_t)k * 8);
-    HIPCHECK(hipMemcpyAsync(c.slot[S_MISC0].p, rows, (size_t)k * 8, hipMemcpyHostToDevice, st));
-    KLAUNCH("k_sa_rows", 0.0, k_sa_rows, dim3(blocks(k)), dim3(256), 0, st, ix->sa.as<uint32_t>(),
-                       c.slot[S_MISC0].as<int64_t>(), k, c.slot[S_MISC1].as<int64_t>());
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(out, c.slot[S_MISC1].p, (size_t)k * 8, hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-}
-
-namespace {
-FM2View fm2_view(const DeviceIndex *ix) {
-    FM2View g;
-    g.blk = ix->fm2.as<uint4>();
-    const char sym[5] = {'A', 'C', 'G', 'T', '$'};
-    for (int q = 0; q < 5; ++q) {
-        g.C[q] = ix->C[(uint8_t)sym[q]];
-        g.tot[q] = ix->totals[(uint8_t)sym[q]];
-    }
-    g.n = ix->n;
-    g.dollar = ix->dollar_row;
-    return g;
-}
-// the byte-Occ view; its C / totals / row tables go up into the S_MISC3 slot
-FMView fm_view(Ctx &c, const DeviceIndex *ix) {
-    hipStream_t st = c.stream;
-    c.slot[S_MISC3].ensure(256 * 8 * 2 + 256);
-    int64_t *tabs = c.slot[S_MISC3].as<int64_t>();
-    HIPCHECK(hipMemcpyAsync(tabs, ix->C, 256 * 8, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(tabs + 256, ix->totals, 256 * 8, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(tabs + 512, ix->code_of, 256, hipMemcpyHostToDevice, st));
-    FMView f;
-    f.bwt = ix->bwt.as<uint8_t>();
-    f.occ = ix->occ.as<int32_t>();
-    f.C = tabs;
-    f.tot = tabs + 256;
-    f.row = (const uint8_t *)(tabs + 512);
-    f.n = ix->n;
-    f.olen = index_occ_len(ix);
-    f.k = ix->occ_sample;
-    return f;
-}
-}  // namespace
-
-void index_backward_search(Ctx &c, DeviceIndex *ix, const uint8_t *pats, const int64_t *off, int64_t npat,
-                           int64_t *sp_ep) {
-    if (npat <= 0) return;
-    hipStream_t st = c.stream;
-    const int64_t plen = off[npat];
-    c.slot[S_MISC0].ensure((size_t)plen + 8);
-    c.slot[S_MISC1].ensure((size_t)(npat + 1) * 8);
-    c.slot[S_MISC2].ensure((size_t)npat * 16);
-    if (plen) HIPCHECK(hipMemcpyAsync(c.slot[S_MISC0].p, pats, (size_t)plen, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(c.slot[S_MISC1].p, off, (size_t)(npat + 1) * 8, hipMemcpyHostToDevice, st));
-    const FMView f = fm_view(c, ix);
-    if (ix->has_fm2 && !knob(KN_FM_BYTES)) {
-        const FM2View g = fm2_view(ix);
-        KLAUNCH("k_bsearch2", 0.0, k_bsearch2, dim3(blocks(npat)), dim3(256), 0, st, g, c.slot[S_MISC0].as<uint8_t>(),
-                c.slot[S_MISC1].as<int64_t>(), npat, c.slot[S_MISC2].as<int64_t>());
-    } else {
-        KLAUNCH("k_bsearch", 0.0, k_bsearch, dim3(blocks(npat)), dim3(256), 0, st, f, c.slot[S_MISC0].as<uint8_t>(),
-                c.slot[S_MISC1].as<int64_t>(), npat, c.slot[S_MISC2].as<int64_t>());
-    }
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(sp_ep, c.slot[S_MISC2].p, (size_t)npat * 16, hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-}
-
-// The locate seed search (locate.hip): exact backward search of np pieces,
-// piece p = d_pats[d_off[p], d_off[p + 1]) (device arrays), through the same
-// rank paths as index_backward_search; the first SA row and the width of every
-// interval stay on the device.  Uses the S_MISC3 slot (byte-Occ tables).
-void index_seed_search_device(Ctx &c, DeviceIndex *ix, const uint8_t *d_pats, const int64_t *d_off, int64_t np,
-                              int64_t plen, int64_t *d_row0, int64_t *d_width) {
-    if (np <= 0) return;
-    hipStream_t st = c.stream;
-    // per piece: its bytes and ~2 rank blocks per byte (gathers), 3 words in / out
-    const double bytes = (double)plen * 65.0 + (double)np * 32.0;
-    if (ix->has_fm2 && !knob(KN_FM_BYTES)) {
-        KLAUNCH("k_loc_seed2", bytes, k_loc_seed2, dim3(blocks(np)), dim3(256), 0, st, fm2_view(ix), d_pats, d_off, np,
-                d_row0, d_width);
-    } else {
-        const FMView f = fm_view(c, ix);
-        KLAUNCH("k_loc_seed", bytes, k_loc_seed, dim3(blocks(np)), dim3(256), 0, st, f, d_pats, d_off, np, d_row0,
-                d_width);
-    }
-    HIPCHECK(hipGetLastError());
-}
-
-// The SMEM search's matching statistics (smem.hip): nl lanes over the ns
-// strings of d_str, d_q their bytes; l(e), the first SA row and the width of
-// every lane stay on the device.  The same choice of rank path as above; uses
-// the S_MISC3 slot (byte-Occ tables).
-void index_smem_ms_device(Ctx &c, DeviceIndex *ix, const uint8_t *d_q, const SmemStr *d_str, int64_t ns, int64_t nl,
-                          double max_steps, int32_t *d_ell, int64_t *d_row0, int64_t *d_width) {
-    if (nl <= 0) return;
-    hipStream_t st = c.stream;
-    // a model, not a count: l(e) is not known before the launch, so every lane
-    // is taken to run its e steps (max_steps = their sum; a read copied from the
-    // text does), a byte and two 32-byte rank blocks each, 20 bytes out.  The
-    // steps really taken are the call's `work`.
-    const double bytes = max_steps * 65.0 + (double)nl * 20.0;
-    if (ix->has_fm2 && !knob(KN_FM_BYTES)) {
-        KLAUNCH("k_smem_ms2", bytes, k_smem_ms2, dim3(blocks(nl)), dim3(256), 0, st, fm2_view(ix), d_q, d_str, ns, nl,
-                d_ell, d_row0, d_width);
-    } else {
-        const FMView f = fm_view(c, ix);
-        KLAUNCH("k_smem_ms", bytes, k_smem_ms, dim3(blocks(nl)), dim3(256), 0, st, f, ix->text.as<uint8_t>(), d_q, d_str,
-                ns, nl, d_ell, d_row0, d_width);
-    }
-    HIPCHECK(hipGetLastError());
 }
 
 }  // namespace bwtmi

@@ -46,8 +46,6 @@ namespace {
 constexpr int kB = 256;
 constexpr int kMaxUnit = 9;   // enumerate_motifs range ends at 9 (bwt.py:2052)
 
-inline unsigned blocks(int64_t n) { return (unsigned)((n + kB - 1) / kB); }
-
 // ------------------------------------------------------------- LCP plateaus
 __global__ void k_max_i32(const int32_t *__restrict__ a, int64_t n, int *__restrict__ out) {
     int v = 0;

@@ -40,7 +40,6 @@ namespace {
 constexpr int kB = 256;
 constexpr int kTile = 4096;
 
-inline unsigned blocks(int64_t n) { return (unsigned)((n + kB - 1) / kB); }
 inline int bits_for(uint64_t v) {
     int b = 0;
     while (b < 64 && (v >> b) != 0) ++b;

@@ -3,7 +3,8 @@ symbols, against the CPU oracle (pinned to the reference on the same kind of
 grid by tests/test_oracle.py::test_index_rates_match_reference).  Integer
 work: every comparison is exact.
 
-The rates select the code that runs (index.hip, sa_dna.hip):
+The rates select the code that runs (index.hip, sa_dna.hip; d_rank's consumers
+in search.hip):
 
   occ_sample 16 .. 1024, a power of two, <= 16 symbols   k_occ_groups<1 .. 64>
   any other rate or more than 16 symbols                k_occ_blocks, with
@@ -125,6 +126,47 @@ class _Launches:
 
     def count(self, name):
         return self.stats.get(name, (0.0, 0, 0.0))[1]
+
+
+def _three_searches(gpu_ctx, core, pats, fm_bytes):
+    """backward_search_batch, locate_batch (k = 1) and smem_batch of pats under
+    BWTMI_FM_BYTES=fm_bytes: the kernel launches, and every array returned."""
+    from bwtmi import _lib
+    with _lib.knobs(FM_BYTES=fm_bytes), _Launches(gpu_ctx) as k:
+        iv = core.backward_search_batch(pats)
+        loc = core.locate_batch(pats, max_mismatches=1, both_strands=True)
+        sm = core.smem_batch(pats, min_len=8, both_strands=True)
+    arrays = [iv, loc.offsets, loc.positions, loc.mismatches, loc.strand, sm.offsets, sm.qstart, sm.qend, sm.strand,
+              sm.count, sm.pos_offsets, sm.positions]
+    return k, [np.asarray(a).tolist() for a in arrays] + [int(loc.candidates), int(sm.positions_total), int(sm.work)]
+
+
+@pytest.mark.parametrize("case", ["packed", "bytes-by-knob", "bytes-by-text"])
+def test_rank_path_dispatch_of_the_three_searches(gpu_ctx, case):
+    """The choice of rank path (search.hip, with_rank) as each of the three
+    searches makes it: one launch of the chosen path's seed kernel under its
+    statistics name and none of its twin -- the packed rank on an ACGT text,
+    the byte rank on the same text under BWTMI_FM_BYTES=1 and on a gap text,
+    which has no packed rank -- and the two paths return the same on the ACGT
+    text."""
+    from bwtmi import BWTCore
+    text = _text("gaps" if case == "bytes-by-text" else "acgt", 2001, 4242)
+    rng = np.random.default_rng(99)
+    pats = []
+    for _ in range(20):
+        m = int(rng.integers(12, 41))
+        a = int(rng.integers(0, len(text) - 1 - m))
+        pats.append(text[a:a + m].decode())
+    core = BWTCore(text, 32, 128)
+    fm_bytes = int(case == "bytes-by-knob")
+    k, got = _three_searches(gpu_ctx, core, pats, fm_bytes)
+    for name in ("k_bsearch", "k_loc_seed", "k_smem_ms"):
+        mine, twin = (name + "2", name) if case == "packed" else (name, name + "2")
+        assert k.count(mine) == 1 and k.count(twin) == 0, (case, name, k.stats.keys())
+    assert all(sp >= 0 for sp, _ in got[0])           # every pattern was cut from the text
+    if case != "bytes-by-text":
+        _, other = _three_searches(gpu_ctx, core, pats, 1 - fm_bytes)
+        assert got == other
 
 
 # ------------------------------------------------------------------ Occ checkpoints

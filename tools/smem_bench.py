@@ -9,7 +9,10 @@ the same run on the same index: each read's substrings through one
 backward_search_batch call, the SMEM rule on the host, locate_positions per
 seed, for as many reads as finish in --route-seconds; equal results asserted.
 
-    python tools/smem_bench.py OUT.json [--route-seconds S]
+    python tools/smem_bench.py OUT.json [--route-seconds S] [--tree DIR]
+
+(--tree: the package of another checkout, as below; the run carries a digest
+of the call's arrays, so that two trees can be held against each other.)
 
 With --untouched: only the searches this feature does not touch (k_bsearch2 /
 k_bsearch over the 145,338 motifs, locate_batch at k = 0 and k = 2), from the
@@ -102,7 +105,10 @@ def smem_runs(ctx, n, nreads, m, nsub, min_len, route_seconds, reps=5):
                positions=int(got.positions.size), positions_total=int(got.positions_total),
                lanes=2 * nreads * m, rank_kernel=rank, rank_kernel_ms=round(ks[rank][0], 4),
                rank_steps_per_ns=round(got.work / (ks[rank][0] * 1e6), 2),
-               wall_us_per_read=round(min(walls) * 1e3 / nreads, 3), kernels=_kern(ks))
+               wall_us_per_read=round(min(walls) * 1e3 / nreads, 3), kernels=_kern(ks),
+               results_sha256=hashlib.sha256(b"".join(
+                   np.ascontiguousarray(a).tobytes() for a in (got.offsets, got.qstart, got.qend, got.strand, got.count,
+                                                               got.pos_offsets, got.positions))).hexdigest()[:16])
     # the route that existed before, on the same index (fresh host state: the SA comes down again)
     core._sa = None
     t0, done = time.perf_counter(), 0
@@ -159,6 +165,7 @@ def untouched(ctx, n=10_000_000):
         out[f"locate_k{k}_wall_ms"] = round(min(walls), 3)
         out[f"locate_k{k}_kernels_ms"] = round(sum(v[0] for v in ks.values()), 4)
         out[f"locate_k{k}_seed_ms"] = round(ks["k_loc_seed2"][0], 4)
+        out[f"locate_k{k}_kernels"] = {name: round(v[0], 4) for name, v in sorted(ks.items())}
         for a in (got.offsets, got.positions, got.mismatches, got.strand):
             h.update(a.tobytes())
     out["results_sha256"] = h.hexdigest()[:16]
