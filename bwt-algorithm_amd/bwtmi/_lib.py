@@ -63,6 +63,7 @@ _SIGS = {
                                        C.c_int32, C.c_int64]),
     "bwtmi_index_build": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(_P)]),
     "bwtmi_index_free": (C.c_int, [_P]),
+    "bwtmi_index_has_reverse": (C.c_int, [_P]),
     "bwtmi_index_size": (C.c_int64, [_P]),
     "bwtmi_index_get_sa": (C.c_int, [_P, _P]),
     "bwtmi_index_get_bwt": (C.c_int, [_P, _P]),
@@ -80,6 +81,8 @@ _SIGS = {
                                            C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bwtmi_index_smem_batch": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_uint32, C.c_int64, C.c_int64] +
                                [C.POINTER(C.c_void_p)] * 7 + [C.POINTER(C.c_int64)] * 4),
+    "bwtmi_index_smem_long_batch": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_uint32, C.c_int64, C.c_int64] +
+                                    [C.POINTER(C.c_void_p)] * 7 + [C.POINTER(C.c_int64)] * 5),
     "bwtmi_index_lcp_plateaus": (C.c_int, [_P, _P, C.POINTER(LibParams), C.POINTER(C.c_void_p),
                                            C.POINTER(C.c_int64)]),
     "bwtmi_index_short_imperfect": (C.c_int, [_P, _P, C.POINTER(LibParams), _P, C.c_int64, _P, C.c_int32]),

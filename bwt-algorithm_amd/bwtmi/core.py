@@ -81,15 +81,17 @@ class SmemResult:
     SMEM, empty where count > max_occ).  result[i] = (qstart, qend, strand,
     count, positions per SMEM) of query i, its SMEMs by (strand, qstart).
     `positions_total` is the call's position count (what max_positions caps),
-    `work` the sum of the matching statistics (the search's rank steps)."""
+    `work` the sum of the matching statistics (smem_batch's rank steps),
+    `steps` the rank steps smem_long_batch really took (0 from smem_batch)."""
 
     __slots__ = ("offsets", "qstart", "qend", "strand", "count", "pos_offsets", "positions", "positions_total",
-                 "work")
+                 "work", "steps")
 
-    def __init__(self, offsets, qstart, qend, strand, count, pos_offsets, positions, positions_total=0, work=0):
+    def __init__(self, offsets, qstart, qend, strand, count, pos_offsets, positions, positions_total=0, work=0,
+                 steps=0):
         self.offsets, self.qstart, self.qend, self.strand, self.count = offsets, qstart, qend, strand, count
         self.pos_offsets, self.positions = pos_offsets, positions
-        self.positions_total, self.work = positions_total, work
+        self.positions_total, self.work, self.steps = positions_total, work, steps
 
     def __len__(self):
         return self.offsets.size - 1
@@ -109,7 +111,11 @@ class BWTCore:
     BITS_TO_BASE = {0: "A", 1: "C", 2: "G", 3: "T"}
 
     def __init__(self, text: Union[str, bytes], sa_sample_rate: int = 32, occ_sample_rate: int = 128,
-                 device: Optional[int] = None, build_kmer: bool = True):
+                 device: Optional[int] = None, build_kmer: bool = True, reverse_index: bool = False):
+        # reverse_index: also build the index of the reversed text that
+        # smem_long_batch steps through (BWTMI_INDEX_REVERSE: the text's last
+        # character must occur once, as the '$' of seq + '$' does; ValueError
+        # otherwise); the build then takes about twice as long
         # bytes are taken as the encoded text itself (no str is built: the CLI
         # hands over the loader's native contig bytes)
         raw = bytes(text) if isinstance(text, (bytes, bytearray, memoryview)) else None
@@ -121,9 +127,14 @@ class BWTCore:
         self._ctx = _lib.ctx(device)
         self._h = C.c_void_p()
         buf = self.text_arr if self.text_arr.size else np.zeros(1, dtype=np.uint8)
-        check(lib().bwtmi_index_build(self._ctx, buf.ctypes.data_as(C.c_void_p), self.text_arr.size,
-                                      sa_sample_rate, occ_sample_rate, 0 if build_kmer else 1,
-                                      C.byref(self._h)))
+        rc = lib().bwtmi_index_build(self._ctx, buf.ctypes.data_as(C.c_void_p), self.text_arr.size,
+                                     sa_sample_rate, occ_sample_rate,
+                                     (0 if build_kmer else 1) | (2 if reverse_index else 0), C.byref(self._h))
+        if rc == -1 and reverse_index:   # BWTMI_E_ARG: the last byte is not unique
+            msg = lib().bwtmi_last_error()
+            raise ValueError(msg.decode(errors="replace") if msg else "bad argument")
+        check(rc)
+        self.has_reverse_index = bool(lib().bwtmi_index_has_reverse(self._h))
         totals = np.zeros(256, dtype=np.int64)
         cum = np.zeros(256, dtype=np.int64)
         check(lib().bwtmi_index_get_counts(self._h, totals.ctypes.data_as(C.c_void_p),
@@ -338,6 +349,21 @@ class BWTCore:
         contract).  ValueError for an empty query, one longer than 1024 bytes
         or min_len < 1; BwtmiError with the position count when it exceeds
         max_positions (default 2^27)."""
+        return self._smem(False, queries, min_len, both_strands, max_occ, max_positions)
+
+    def smem_long_batch(self, queries: Sequence[Union[str, bytes]], min_len: int = 1, both_strands: bool = False,
+                        max_occ: Optional[int] = None, max_positions: Optional[int] = None) -> "SmemResult":
+        """smem_batch for long reads: the same contract and, for queries that
+        both accept, the same result, for queries of up to 1,048,576 bytes
+        (include/bwtmi.h, bwtmi_index_smem_long_batch).  The index must have
+        been built with reverse_index=True (BwtmiError otherwise).  The
+        result's `steps` is the rank steps taken: linear in the read length
+        when the read matches in a few long stretches, quadratic again when
+        its SMEMs overlap almost completely (a repeat tract longer than the
+        text's)."""
+        return self._smem(True, queries, min_len, both_strands, max_occ, max_positions)
+
+    def _smem(self, long_entry, queries, min_len, both_strands, max_occ, max_positions) -> "SmemResult":
         for name, v in (("max_occ", max_occ), ("max_positions", max_positions)):
             if v is not None and int(v) <= 0:
                 raise ValueError(f"{name} must be positive")
@@ -347,13 +373,12 @@ class BWTCore:
         blob = np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8)
         nq = off.size - 1
         ptrs = [C.c_void_p() for _ in range(7)]
-        ns, npos, total, work = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        rc = lib().bwtmi_index_smem_batch(self._ctx, self._h, blob.ctypes.data_as(C.c_void_p),
-                                          off.ctypes.data_as(C.c_void_p), nq, int(min_len), 1 if both_strands else 0,
-                                          0 if max_occ is None else int(max_occ),
-                                          0 if max_positions is None else int(max_positions),
-                                          *[C.byref(p) for p in ptrs], C.byref(ns), C.byref(npos), C.byref(total),
-                                          C.byref(work))
+        ns, npos, total, work, steps = (C.c_int64(0) for _ in range(5))
+        entry = lib().bwtmi_index_smem_long_batch if long_entry else lib().bwtmi_index_smem_batch
+        rc = entry(self._ctx, self._h, blob.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), nq,
+                   int(min_len), 1 if both_strands else 0, 0 if max_occ is None else int(max_occ),
+                   0 if max_positions is None else int(max_positions), *[C.byref(p) for p in ptrs], C.byref(ns),
+                   C.byref(npos), C.byref(total), C.byref(work), *([C.byref(steps)] if long_entry else []))
         if rc == -1:   # BWTMI_E_ARG
             msg = lib().bwtmi_last_error()
             raise ValueError(msg.decode(errors="replace") if msg else "bad argument")
@@ -367,7 +392,7 @@ class BWTCore:
             n = ns.value
             return SmemResult(take(ptrs[0], np.int64, nq + 1), take(ptrs[1], np.int32, n), take(ptrs[2], np.int32, n),
                               take(ptrs[3], np.uint8, n), take(ptrs[4], np.int64, n), take(ptrs[5], np.int64, n + 1),
-                              take(ptrs[6], np.int64, npos.value), total.value, work.value)
+                              take(ptrs[6], np.int64, npos.value), total.value, work.value, steps.value)
         finally:
             for p in ptrs:
                 lib().bwtmi_free(p)

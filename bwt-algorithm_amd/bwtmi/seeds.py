@@ -2,7 +2,7 @@
 against a genome, with where they occur -- the seeds a read mapper, an STR
 genotyper or a contamination screen starts from.
 
-    python seeds.py IN.fa QUERIES [-l MIN_LEN] [--both-strands] [--max-occ N] [--max-positions N] -o OUT.tsv
+    python seeds.py IN.fa QUERIES [-l MIN_LEN] [--both-strands] [--long] [--max-occ N] [--max-positions N] -o OUT.tsv
 
 QUERIES is in the pattern-file format of `locate.py` (`SEQ` or `NAME<TAB>SEQ`
 per line).  One FM index per contig (seq + '$', built on the device, released
@@ -11,8 +11,11 @@ contig, `query qstart qend strand chrom count positions`, ordered by contig,
 then query order in the file, then (strand, qstart).  `positions` is
 comma-joined, or `*` when count > max-occ.  Maximality is per contig: each
 contig has its own index, so a match that could be extended on another contig
-is still reported on the one where it cannot.  Not in the reference: `bwt.py`
-stays the drop-in, this tool stands next to it.
+is still reported on the one where it cannot.  Queries are at most 1024 bp;
+with `--long`, 1,048,576 bp: each contig's index is then built with its reverse
+index (about twice the build time) and searched by BWTCore.smem_long_batch,
+with the same rows in the same order.  Not in the reference: `bwt.py` stays
+the drop-in, this tool stands next to it.
 """
 from __future__ import annotations
 
@@ -44,9 +47,12 @@ def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(
         description="Super-maximal exact matches of reads against a genome (MI355X-native FM index)")
     p.add_argument("reference", help="Reference genome FASTA file")
-    p.add_argument("queries", help="Query file: one SEQ or NAME<TAB>SEQ per line ('#' comments), up to 1024 bp each")
+    p.add_argument("queries", help="Query file: one SEQ or NAME<TAB>SEQ per line ('#' comments), up to 1024 bp each "
+                                   "(1,048,576 with --long)")
     p.add_argument("-l", "--min-len", type=int, default=19, help="Shortest SMEM reported (default: 19)")
     p.add_argument("--both-strands", action="store_true", help="Also search the reverse complement")
+    p.add_argument("--long", action="store_true",
+                   help="Long reads: build each contig's reverse index too and lift the 1024 bp limit to 1,048,576 bp")
     p.add_argument("--max-occ", type=int, default=1024,
                    help="List the positions of an SMEM with at most this many occurrences, else '*' (default: 1024)")
     p.add_argument("--max-positions", type=int, default=None,
@@ -69,9 +75,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         with open(tmp, "w") as out:
             for cid in range(job.contig_count()):
                 chrom = job.contig_info(cid)[0]
-                core = BWTCore(job.contig_seq(cid) + b"$", build_kmer=False)
+                core = BWTCore(job.contig_seq(cid) + b"$", build_kmer=False, reverse_index=a.long)
                 try:
-                    res = core.smem_batch(seqs, a.min_len, a.both_strands, a.max_occ, a.max_positions)
+                    search = core.smem_long_batch if a.long else core.smem_batch
+                    res = search(seqs, a.min_len, a.both_strands, a.max_occ, a.max_positions)
                 finally:
                     core.clear()
                 out.writelines(smem_rows(chrom, names, res, a.max_occ))

@@ -649,6 +649,7 @@ int bwtmi_index_free(bwtmi_index *idx) {
 }
 
 int64_t bwtmi_index_size(const bwtmi_index *idx) { return idx ? index_n(idx->d) : -1; }
+int bwtmi_index_has_reverse(const bwtmi_index *idx) { return idx && index_has_reverse(idx->d) ? 1 : 0; }
 int64_t bwtmi_index_occ_len(const bwtmi_index *idx) { return idx ? index_occ_len(idx->d) : -1; }
 int64_t bwtmi_index_sampled_len(const bwtmi_index *idx) { return idx ? index_sampled_len(idx->d) : -1; }
 int64_t bwtmi_index_kmer_count(const bwtmi_index *idx) { return idx ? index_kmer_count(idx->d) : -1; }
@@ -719,11 +720,16 @@ int bwtmi_index_locate_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *pa
     });
 }
 
-int bwtmi_index_smem_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
-                           int32_t min_len, uint32_t flags, int64_t max_occ, int64_t max_positions, int64_t **smem_off,
-                           int32_t **qstart, int32_t **qend, uint8_t **strand, int64_t **count, int64_t **pos_off,
-                           int64_t **pos, int64_t *nsmem, int64_t *npos, int64_t *positions_total, int64_t *work) {
+// the two SMEM entries: `search` is index_smem_batch or index_smem_long_batch
+using SmemSearch = void (*)(Ctx &, DeviceIndex *, const uint8_t *, const int64_t *, int64_t, int32_t, bool, int64_t,
+                            int64_t, SmemResult &);
+static int smem_entry(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                      int32_t min_len, uint32_t flags, int64_t max_occ, int64_t max_positions, int64_t **smem_off,
+                      int32_t **qstart, int32_t **qend, uint8_t **strand, int64_t **count, int64_t **pos_off,
+                      int64_t **pos, int64_t *nsmem, int64_t *npos, int64_t *positions_total, int64_t *work,
+                      int64_t *steps, SmemSearch search) {
     return guard([&] {
+        if (steps) *steps = 0;
         CHECK_ARG(ctx && idx && off && smem_off && qstart && qend && strand && count && pos_off && pos && nsmem && npos &&
                       nq >= 0,
                   "bad argument");
@@ -738,14 +744,15 @@ int bwtmi_index_smem_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, 
         use(ctx->c);
         SmemResult r;
         try {
-            index_smem_batch(ctx->c, idx->d, qs, off, nq, min_len, (flags & BWTMI_SMEM_BOTH_STRANDS) != 0, max_occ,
-                             max_positions, r);
+            search(ctx->c, idx->d, qs, off, nq, min_len, (flags & BWTMI_SMEM_BOTH_STRANDS) != 0, max_occ, max_positions,
+                   r);
         } catch (...) {
             if (positions_total) *positions_total = r.positions_total;   // the count a tripped cap reports
             throw;
         }
         if (positions_total) *positions_total = r.positions_total;
         if (work) *work = r.work;
+        if (steps) *steps = r.steps;
         *smem_off = malloc_copy(r.smem_off);
         *qstart = malloc_copy(r.qstart);
         *qend = malloc_copy(r.qend);
@@ -756,6 +763,23 @@ int bwtmi_index_smem_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, 
         *nsmem = (int64_t)r.qstart.size();
         *npos = (int64_t)r.pos.size();
     });
+}
+
+int bwtmi_index_smem_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                           int32_t min_len, uint32_t flags, int64_t max_occ, int64_t max_positions, int64_t **smem_off,
+                           int32_t **qstart, int32_t **qend, uint8_t **strand, int64_t **count, int64_t **pos_off,
+                           int64_t **pos, int64_t *nsmem, int64_t *npos, int64_t *positions_total, int64_t *work) {
+    return smem_entry(ctx, idx, qs, off, nq, min_len, flags, max_occ, max_positions, smem_off, qstart, qend, strand, count,
+                      pos_off, pos, nsmem, npos, positions_total, work, nullptr, index_smem_batch);
+}
+
+int bwtmi_index_smem_long_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                                int32_t min_len, uint32_t flags, int64_t max_occ, int64_t max_positions,
+                                int64_t **smem_off, int32_t **qstart, int32_t **qend, uint8_t **strand,
+                                int64_t **count, int64_t **pos_off, int64_t **pos, int64_t *nsmem, int64_t *npos,
+                                int64_t *positions_total, int64_t *work, int64_t *steps) {
+    return smem_entry(ctx, idx, qs, off, nq, min_len, flags, max_occ, max_positions, smem_off, qstart, qend, strand, count,
+                      pos_off, pos, nsmem, npos, positions_total, work, steps, index_smem_long_batch);
 }
 
 static LibParams lib_params(const bwtmi_lib_params *p) {

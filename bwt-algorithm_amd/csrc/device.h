@@ -402,12 +402,17 @@ struct DeviceIndex {
     DBuf fm2;
     bool has_fm2 = false;
     int64_t dollar_row = -1;
+    // BWTMI_INDEX_REVERSE: the rank structures of a second index, over
+    // reverse(T[0, n-1)) + T[n-1] (its text, SA and samples are released after
+    // the build: the long SMEM search only steps through it); else nullptr
+    DeviceIndex *rev = nullptr;
 };
 // d_text: device text incl. sentinel, n bytes (padded by >= 64 bytes)
 DeviceIndex *index_build_device(Ctx &c, const uint8_t *d_text, int64_t n, int32_t sa_sample,
                                 int32_t occ_sample, uint32_t flags, DeviceIndex *reuse = nullptr);
 void index_free(DeviceIndex *);
 int64_t index_n(const DeviceIndex *);
+bool index_has_reverse(const DeviceIndex *);
 int64_t index_occ_len(const DeviceIndex *);
 int64_t index_sampled_len(const DeviceIndex *);
 int64_t index_kmer_count(const DeviceIndex *);
@@ -466,8 +471,13 @@ struct SmemResult {
     std::vector<int64_t> count;
     std::vector<int64_t> pos_off, pos;     // nsmem + 1 offsets; positions
     int64_t positions_total = 0, work = 0;
+    int64_t steps = 0;                     // the long entry: rank steps taken
 };
 void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq, int32_t min_len,
                       bool both_strands, int64_t max_occ, int64_t max_positions, SmemResult &out);
+// the same for queries of up to 2^20 bytes, over an index built with BWTMI_INDEX_REVERSE
+void index_smem_long_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq,
+                           int32_t min_len, bool both_strands, int64_t max_occ, int64_t max_positions,
+                           SmemResult &out);
 
 }  // namespace bwtmi

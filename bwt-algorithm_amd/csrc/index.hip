@@ -123,6 +123,12 @@ __global__ void k_gid(const uint32_t *__restrict__ head_scan_excl, const uint32_
     gid[r] = head_scan_excl[r] + head[r] - 1u;
 }
 
+// R = reverse(T[0, n-1)) + T[n-1]: the text of the reverse index
+__global__ __launch_bounds__(256) void k_reverse_text(const uint8_t *__restrict__ t, int64_t n, uint8_t *__restrict__ r) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) r[i] = t[i == n - 1 ? i : n - 2 - i];
+}
+
 __global__ __launch_bounds__(256) void k_bwt(const uint8_t *__restrict__ t, const uint32_t *__restrict__ sa, int64_t n,
                                              uint8_t *__restrict__ bwt) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -500,6 +506,11 @@ void sa_doubling(Ctx &c, DeviceIndex *ix, const uint8_t *T, int64_t n, int sigma
 DeviceIndex *index_build_device(Ctx &c, const uint8_t *d_text, int64_t n, int32_t sa_sample, int32_t occ_sample,
                                 uint32_t flags, DeviceIndex *reuse) {
     auto *ix = reuse ? reuse : new DeviceIndex();   // reuse: keep the buffers of an earlier build
+    const bool reverse = (flags & BWTMI_INDEX_REVERSE) != 0;
+    if (!reverse && ix->rev) {
+        index_free(ix->rev);
+        ix->rev = nullptr;
+    }
     ix->has_kmer = false;
     ix->kmer_count = 0;
     hipStream_t st = c.stream;
@@ -532,6 +543,18 @@ DeviceIndex *index_build_device(Ctx &c, const uint8_t *d_text, int64_t n, int32_
         }
     }
     ix->sigma = sigma;
+    if (reverse) {   // the reverse text must end with the one byte that nothing follows
+        uint8_t z = 0;
+        if (n) {
+            HIPCHECK(hipMemcpyAsync(&z, T + n - 1, 1, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipStreamSynchronize(st));
+        }
+        if (n < 1 || ix->totals[z] != 1) {
+            if (!reuse) index_free(ix);
+            fail(BWTMI_E_ARG, "index: BWTMI_INDEX_REVERSE needs a text whose last byte occurs once (n = %lld)",
+                 (long long)n);
+        }
+    }
     ix->sa.ensure((size_t)std::max<int64_t>(n, 1) * 4);
     ix->occ_len = ix->sampled_len = 0;
     if (n == 0) return ix;
@@ -668,12 +691,34 @@ DeviceIndex *index_build_device(Ctx &c, const uint8_t *d_text, int64_t n, int32_
     HIPCHECK(hipStreamSynchronize(st));
     c.checks_verify("the end of the index build");
     c.kresolve();
+    if (reverse) {
+        // the same build over R (same sample rates, no k-mer table); only its rank
+        // structures are kept
+        DBuf rt;
+        try {
+            rt.ensure((size_t)n + 128);
+            HIPCHECK(hipMemsetAsync(rt.p, 0, (size_t)n + 128, st));
+            KLAUNCH("k_reverse_text", 2.0 * (double)n, k_reverse_text, dim3(blocks(n)), dim3(256), 0, st, T, n,
+                    rt.as<uint8_t>());
+            ix->rev = index_build_device(c, rt.as<uint8_t>(), n, sa_sample, occ_sample, BWTMI_INDEX_NO_KMER, ix->rev);
+        } catch (...) {
+            (void)hipDeviceSynchronize();
+            rt.release();
+            throw;
+        }
+        rt.release();   // (the inner build ended on a stream wait)
+        ix->rev->text.release();
+        ix->rev->sa.release();
+        ix->rev->sampled.release();
+        ix->rev->sampled_len = 0;
+    }
     return ix;
 }
 
 void index_free(DeviceIndex *ix) {
     if (!ix) return;
     (void)hipDeviceSynchronize();
+    index_free(ix->rev);
     ix->text.release();
     ix->sa.release();
     ix->bwt.release();
@@ -686,6 +731,7 @@ void index_free(DeviceIndex *ix) {
 }
 
 int64_t index_n(const DeviceIndex *ix) { return ix->n; }
+bool index_has_reverse(const DeviceIndex *ix) { return ix->rev != nullptr; }
 int64_t index_occ_len(const DeviceIndex *ix) { return ix->n ? ix->occ_len : 0; }
 int64_t index_sampled_len(const DeviceIndex *ix) { return ix->sampled_len; }
 int64_t index_kmer_count(const DeviceIndex *ix) { return ix->kmer_count; }

@@ -40,6 +40,11 @@
 //   k_smem_occ      one lane per reported position: (SMEM << posbits) | SA value
 //   sort            radix_sort_pairs32 over the key bits in use
 //   k_smem_unpack   keys -> positions
+// Long reads (index_smem_long_batch, an index with its reverse index): the
+// matching statistics come from k_smem_walk instead, one lane per searched
+// string, which walks the string's SMEMs left to right -- rightwards in the
+// reverse index, leftwards in the forward one -- and fills the same three
+// per-lane arrays; everything from k_smem_flag on is shared.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,6 +62,7 @@ constexpr int kLocMaxMismatch = 3;
 constexpr int64_t kLocMaxPattern = 1024;
 constexpr int64_t kLocDefaultCap = int64_t{1} << 27;
 constexpr int64_t kSmemMaxQuery = 1024;
+constexpr int64_t kSmemMaxLongQuery = int64_t{1} << 20;
 constexpr int64_t kSmemDefaultMaxOcc = 1024;
 
 // ---- packed FM rank for ACGT* '$' texts (bwt.py:335-357 semantics)
@@ -187,10 +193,12 @@ FM2View fm2_view(const DeviceIndex *ix) {
     return g;
 }
 // the byte-Occ view; its C / totals / row tables go up into the S_MISC3 slot
-FMView fm_view(Ctx &c, const DeviceIndex *ix) {
+// (place 1: the tables of a second view that is live beside the first)
+constexpr size_t kFmTabBytes = 256 * 8 * 2 + 256;
+FMView fm_view(Ctx &c, const DeviceIndex *ix, int place = 0) {
     hipStream_t st = c.stream;
-    c.slot[S_MISC3].ensure(256 * 8 * 2 + 256);
-    int64_t *tabs = c.slot[S_MISC3].as<int64_t>();
+    c.slot[S_MISC3].ensure(2 * kFmTabBytes);
+    int64_t *tabs = reinterpret_cast<int64_t *>(c.slot[S_MISC3].as<uint8_t>() + place * kFmTabBytes);
     HIPCHECK(hipMemcpyAsync(tabs, ix->C, 256 * 8, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(tabs + 256, ix->totals, 256 * 8, hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(tabs + 512, ix->code_of, 256, hipMemcpyHostToDevice, st));
@@ -210,9 +218,9 @@ FMView fm_view(Ctx &c, const DeviceIndex *ix) {
 // index has it and BWTMI_FM_BYTES does not forbid it, else with the byte rank
 // (whose tables then go up into S_MISC3).  `Rank::packed` names the kernel.
 template <class Launch>
-void with_rank(Ctx &c, const DeviceIndex *ix, Launch &&launch) {
+void with_rank(Ctx &c, const DeviceIndex *ix, Launch &&launch, int place = 0) {
     if (ix->has_fm2 && !knob(KN_FM_BYTES)) launch(fm2_view(ix));
-    else launch(fm_view(c, ix));
+    else launch(fm_view(c, ix, place));
 }
 
 // The interval that owns element t of a scanned offset array of `count`
@@ -400,9 +408,11 @@ __global__ __launch_bounds__(256) void k_loc_unpack(const uint64_t *__restrict__
 struct SmemStr {
     int64_t qoff;
     int32_t query;
-    uint32_t info;   // m (11 bits) | strand << 11
+    uint32_t info;   // m (24 bits) | strand << 24
 };
-static_assert(kSmemMaxQuery <= 1024, "SmemStr::info field widths");
+constexpr uint32_t kSmemLenMask = (1u << 24) - 1u;
+constexpr int kSmemStrandBit = 24;
+static_assert(kSmemMaxQuery <= kSmemLenMask && kSmemMaxLongQuery <= kSmemLenMask, "SmemStr::info field widths");
 
 // Lane g is byte g of the strings laid back to back: its string (str: ns
 // entries ascending by qoff, str[0].qoff = 0) and its end e in 1..m.  A '+'
@@ -410,8 +420,8 @@ static_assert(kSmemMaxQuery <= 1024, "SmemStr::info field widths");
 // is (query, strand, qstart) order.
 __device__ __forceinline__ int smem_lane(const SmemStr *__restrict__ str, int64_t ns, int64_t g, SmemStr &s) {
     s = str[owner_of(ns, g, [&](int64_t i) { return str[i].qoff; })];
-    const int m = (int)(s.info & 2047u), t = (int)(g - s.qoff);
-    return (s.info >> 11) & 1u ? m - t : t + 1;
+    const int m = (int)(s.info & kSmemLenMask), t = (int)(g - s.qoff);
+    return (s.info >> kSmemStrandBit) & 1u ? m - t : t + 1;
 }
 
 // Matching statistics, one lane per (searched string, end e).  The lane
@@ -442,6 +452,87 @@ __global__ __launch_bounds__(256) void k_smem_ms(Rank f, const uint8_t *__restri
     width[g] = ep - sp + 1;
 }
 
+// Matching statistics of long strings, one lane per searched string t (an
+// index with its reverse index r, over R = reverse(T[0, n-1)) + z, z = T[n-1]).
+// The lane walks the string's SMEMs left to right.  From a start i:
+//   F  extend Q[i, j) rightwards while it occurs: the backward search of
+//      reverse(Q[i, j)) in r, one plain step per byte.  A step by z finds the
+//      row that wraps in R exactly when the match so far ends T[0, n-1), the
+//      legitimate "...z" match, and nothing follows z: the extension stops.
+//      A string that starts at z has j = i + 1.
+//   l(e) = e - i for every end e not yet written up to j, no search needed:
+//      s(e) = e - l(e) never decreases, i = s(previous j + 1), Q[i, j) occurs.
+//   B(j)    [i, j) is an SMEM when long enough: its SA interval from the
+//      backward search of Q[i, j) in f (start and smem_step, as k_smem_ms),
+//      skipped when j - i < min_len (k_smem_flag reads no width there).
+//   B(j+1)  the next start s(j + 1) = j + 1 - l(j + 1): the backward search
+//      from Q[j] in f, which is known to fail at Q[i] at the latest.
+// It writes what k_smem_ms writes, at the lanes smem_lane defines: ell at every
+// end, row0 / width at the ends j it visits with j - i >= min_len (elsewhere
+// they are not read).  steps[t] = the rank steps taken, failing ones included.
+// Every loop ends on the lane's own bytes and intervals only.
+template <class RankF, class RankR>
+__global__ __launch_bounds__(256) void k_smem_walk(RankF f, RankR r, const uint8_t *__restrict__ text,
+                                                   const uint8_t *__restrict__ q, const SmemStr *__restrict__ str,
+                                                   int64_t ns, int min_len, int32_t *__restrict__ ell,
+                                                   int64_t *__restrict__ row0, int64_t *__restrict__ width,
+                                                   int64_t *__restrict__ steps) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ns) return;
+    const SmemStr s = str[t];
+    const int m = (int)(s.info & kSmemLenMask);
+    const bool minus = (s.info >> kSmemStrandBit) & 1u;
+    const uint8_t *__restrict__ qq = q + s.qoff;
+    const uint8_t z = text[f.n - 1], last = f.last_byte(text);
+    // the lane of end e (smem_lane's rule): 0 <= . < m past qoff for e in 1..m
+    auto at = [&](int e) { return s.qoff + (minus ? m - e : e - 1); };
+    int64_t nstep = 0, sp = 0, ep = -1;
+    int i = 0, done = 0;   // ends 1..done are written; done >= i - 1
+    while (i < m) {
+        int j = i;
+        if (r.start(qq[i], sp, ep)) {
+            j = i + 1;
+            if (qq[i] != z)
+                while (j < m) {
+                    const uint8_t b = qq[j];
+                    ++nstep;
+                    if (!r.step(b, sp, ep)) break;
+                    ++j;
+                    if (b == z) break;
+                }
+        }
+        if (j == i) {   // Q[i] occurs nowhere: l(i + 1) = 0 (and l(i) = 0 where Q[i - 1] does not either)
+            for (int e = done + 1; e <= i + 1; ++e) ell[at(e)] = 0;
+            done = ++i;
+            continue;
+        }
+        for (int e = done + 1; e <= j; ++e) ell[at(e)] = e - i;
+        done = j;
+        if (j - i >= min_len) {
+            f.start(qq[j - 1], sp, ep);
+            for (int k = j - 2; k >= i; --k) {
+                ++nstep;
+                f.smem_step(qq[k], last, sp, ep);
+            }
+            row0[at(j)] = sp;
+            width[at(j)] = ep - sp + 1;
+        }
+        if (j == m) break;
+        int l = 0;
+        if (f.start(qq[j], sp, ep)) {
+            l = 1;
+            for (int k = j - 1; k > i; --k) {   // (Q[i, j + 1) does not occur)
+                ++nstep;
+                if (!f.smem_step(qq[k], last, sp, ep)) break;
+                ++l;
+            }
+        }
+        i = j + 1 - l;
+    }
+    for (int e = done + 1; e <= m; ++e) ell[at(e)] = 0;   // (the last byte occurs nowhere)
+    steps[t] = nstep;
+}
+
 // Lanes 0 .. nl; lane nl writes the scans' last word.  l(e + 1) is the next
 // lane of a '+' string and the previous lane of a '-' string; the lane of
 // e = m has none and flags on its own l.
@@ -456,11 +547,11 @@ __global__ __launch_bounds__(256) void k_smem_flag(const SmemStr *__restrict__ s
     if (g < nl) {
         SmemStr s;
         const int e = smem_lane(str, ns, g, s);
-        const int m = (int)(s.info & 2047u);
+        const int m = (int)(s.info & kSmemLenMask);
         l = ell[g];
         if (l >= min_len) {
             if (e == m) f = 1;
-            else f = ell[(s.info >> 11) & 1u ? g - 1 : g + 1] <= l;
+            else f = ell[(s.info >> kSmemStrandBit) & 1u ? g - 1 : g + 1] <= l;
         }
         if (f) {
             w = width[g];
@@ -498,8 +589,8 @@ __global__ __launch_bounds__(256) void k_smem_compact(const SmemStr *__restrict_
     if (fscan[g + 1] == i || i >= nsmem) return;
     SmemStr s;
     const int e = smem_lane(str, ns, g, s);
-    const int m = (int)(s.info & 2047u), l = ell[g];
-    const bool minus = (s.info >> 11) & 1u;
+    const int m = (int)(s.info & kSmemLenMask), l = ell[g];
+    const bool minus = (s.info >> kSmemStrandBit) & 1u;
     qstart[i] = minus ? m - e : e - l;
     qend[i] = minus ? m - e + l : e;
     strand[i] = minus ? 1 : 0;
@@ -691,8 +782,13 @@ void index_locate_batch(Ctx &c, DeviceIndex *ix, const uint8_t *pats, const int6
     HIPCHECK(hipStreamSynchronize(st));
 }
 
-void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq, int32_t min_len,
-                      bool both_strands, int64_t max_occ, int64_t max_positions, SmemResult &out) {
+namespace {
+
+// the two SMEM entries: long_entry = matching statistics by k_smem_walk over the
+// index's reverse index (queries up to kSmemMaxLongQuery), else by k_smem_ms
+void smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq, int32_t min_len,
+                bool both_strands, int64_t max_occ, int64_t max_positions, bool long_entry, SmemResult &out) {
+    const int64_t max_query = long_entry ? kSmemMaxLongQuery : kSmemMaxQuery;
     if (nq < 0) fail(BWTMI_E_ARG, "smem: negative query count");
     if (min_len < 1) fail(BWTMI_E_ARG, "smem: min_len %d is below 1", min_len);
     if (max_occ <= 0) max_occ = kSmemDefaultMaxOcc;
@@ -705,7 +801,9 @@ void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t 
     out.count.clear();
     out.pos_off.assign(1, 0);
     out.pos.clear();
-    out.positions_total = out.work = 0;
+    out.positions_total = out.work = out.steps = 0;
+    if (long_entry && !ix->rev)
+        fail(BWTMI_E_STATE, "smem: the index has no reverse index (build it with BWTMI_INDEX_REVERSE)");
 
     // ---- string table: Q, then revcomp(Q) where it is searched; string s is bytes [qoff, qoff + m)
     std::vector<uint8_t> qbytes;
@@ -716,14 +814,14 @@ void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t 
     for (int64_t q = 0; q < nq; ++q) {
         const int64_t a = off[q], m = off[q + 1] - a;
         if (m <= 0) fail(BWTMI_E_ARG, "smem: query %lld is empty", (long long)q);
-        if (m > kSmemMaxQuery)
+        if (m > max_query)
             fail(BWTMI_E_ARG, "smem: query %lld has %lld bytes, more than the supported %lld", (long long)q,
-                 (long long)m, (long long)kSmemMaxQuery);
+                 (long long)m, (long long)max_query);
         qlane[(size_t)q] = (int64_t)qbytes.size();
         const int strands = strand_strings(qs + a, m, both_strands, rc);
         for (int s = 0; s < strands; ++s) {
             const uint8_t *src = s ? rc.data() : qs + a;
-            strs.push_back({(int64_t)qbytes.size(), (int32_t)q, (uint32_t)m | (uint32_t)s << 11});
+            strs.push_back({(int64_t)qbytes.size(), (int32_t)q, (uint32_t)m | (uint32_t)s << kSmemStrandBit});
             qbytes.insert(qbytes.end(), src, src + m);
             max_steps += 0.5 * (double)m * (double)(m + 1);
         }
@@ -759,7 +857,25 @@ void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t 
 
     // ---- matching statistics (the rank paths of index_backward_search), flags, the three
     // scans; their totals against the cap
-    with_rank(c, ix, [&](const auto &f) {
+    int64_t *d_steps = nullptr;
+    if (long_entry) {
+        c.slot[S_IDX10].ensure((size_t)ns * 8);
+        d_steps = c.slot[S_IDX10].as<int64_t>();
+        with_rank(c, ix, [&](const auto &f) {
+            with_rank(c, ix->rev, [&](const auto &r) {
+                using RankF = std::decay_t<decltype(f)>;
+                using RankR = std::decay_t<decltype(r)>;
+                // a model: a string that matches in a few long stretches takes ~3 steps
+                // per byte (F, B(j), B(j + 1)), a byte and two 32-byte rank blocks each,
+                // and writes l(e) for every end; the steps really taken are `steps`.
+                // 64 lanes a workgroup: a lane is a whole string, so the strings spread
+                // over as many CUs as there are waves
+                KLAUNCH(RankF::packed ? "k_smem_walk2" : "k_smem_walk", (double)nl * (3.0 * 65.0 + 4.0) + (double)ns * 28.0,
+                        (k_smem_walk<RankF, RankR>), dim3(blocks(ns, 64)), dim3(64), 0, st, f, r, ix->text.as<uint8_t>(),
+                        d_q, d_str, ns, (int)min_len, d_ell, d_row0, d_width, d_steps);
+            }, 1);
+        });
+    } else with_rank(c, ix, [&](const auto &f) {
         using Rank = std::decay_t<decltype(f)>;
         // a model, not a count: l(e) is not known before the launch, so every lane
         // is taken to run its e steps (max_steps = their sum; a read copied from the
@@ -780,9 +896,15 @@ void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t 
     HIPCHECK(hipMemcpyAsync(mb, d_fscan + nl, 8, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(mb + 1, d_wscan + nl, 8, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(mb + 2, d_gscan + nl, 8, hipMemcpyDeviceToHost, st));
+    std::vector<int64_t> lane_steps;
+    if (long_entry) {
+        lane_steps.resize((size_t)ns);
+        HIPCHECK(hipMemcpyAsync(lane_steps.data(), d_steps, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
+    }
     scan_wait(st);   // (the uploads above read pageable host vectors: they are done too)
     const int64_t nsmem = mb[0], npos = mb[2];
     out.work = mb[1];
+    for (int64_t v : lane_steps) out.steps += v;
     out.positions_total = npos;
     if (nsmem < 0 || nsmem > nl || npos < 0)
         fail(BWTMI_E_STATE, "smem: %lld SMEMs with %lld positions out of %lld lanes", (long long)nsmem, (long long)npos,
@@ -840,6 +962,19 @@ void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t 
     HIPCHECK(hipMemcpyAsync(out.pos_off.data(), d_poff, (size_t)(nsmem + 1) * 8, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(out.smem_off.data(), d_soff, (size_t)(nq + 1) * 8, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
+}
+
+}  // namespace
+
+void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq, int32_t min_len,
+                      bool both_strands, int64_t max_occ, int64_t max_positions, SmemResult &out) {
+    smem_batch(c, ix, qs, off, nq, min_len, both_strands, max_occ, max_positions, false, out);
+}
+
+void index_smem_long_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq,
+                           int32_t min_len, bool both_strands, int64_t max_occ, int64_t max_positions,
+                           SmemResult &out) {
+    smem_batch(c, ix, qs, off, nq, min_len, both_strands, max_occ, max_positions, true, out);
 }
 
 }  // namespace bwtmi

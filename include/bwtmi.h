@@ -200,10 +200,27 @@ int bwtmi_exclusive_scan(bwtmi_ctx *ctx, int32_t kind, const void *in, void *out
  * (328-333) and the 8-mer hash (138-171).  text includes the sentinel, exactly
  * as the reference receives it (seq + '$'). */
 #define BWTMI_INDEX_NO_KMER 1u
+/* BWTMI_INDEX_REVERSE: after the forward build, also build a second index over
+ * R = reverse(T[0, n-1)) + T[n-1] on the device, from the resident text, with
+ * the same sample rates and no k-mer table; it is held inside the index and
+ * released by bwtmi_index_free.  bwtmi_index_smem_long_batch needs it; nothing
+ * else reads it, and without the flag the build and every getter are as they
+ * were (with it the getters still return the forward index).  Requires n >= 1
+ * and that T[n-1] occurs exactly once in T (seq + '$' always does), else
+ * BWTMI_E_ARG and nothing is built.  The build runs the suffix sort twice, so
+ * its time roughly doubles; of the reverse index only the rank structures are
+ * kept (BWT, Occ checkpoints, packed blocks): about 1.7 n bytes more on an ACGT
+ * text at the default rates, beside a forward index of about 6.8 n without its
+ * k-mer table.  While the reverse build runs, its text, suffix array and
+ * samples (5.1 n more) are resident too, so the build's peak device memory is
+ * nearly twice the forward index's. */
+#define BWTMI_INDEX_REVERSE 2u
 
 int bwtmi_index_build(bwtmi_ctx *ctx, const uint8_t *text, int64_t n, int32_t sa_sample,
                       int32_t occ_sample, uint32_t flags, bwtmi_index **out);
 int bwtmi_index_free(bwtmi_index *idx);
+/* 1 when the index was built with BWTMI_INDEX_REVERSE, else 0 (NULL: 0) */
+int bwtmi_index_has_reverse(const bwtmi_index *idx);
 int64_t bwtmi_index_size(const bwtmi_index *idx);
 int bwtmi_index_get_sa(const bwtmi_index *idx, int32_t *sa /* n */);
 int bwtmi_index_get_bwt(const bwtmi_index *idx, uint8_t *bwt /* n */);
@@ -338,8 +355,8 @@ int bwtmi_index_locate_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *pa
  *            is legal (smem_off = [0], pos_off = [0]), and so is min_len > m (no
  *            SMEMs).
  * One lane per end costs the sum of l(e) rank steps, m^2 / 2 for a read copied
- * from the text: hence the 1024-byte limit.  Longer reads need a bidirectional
- * index, which this library does not have.
+ * from the text: hence the 1024-byte limit.  Longer reads go through
+ * bwtmi_index_smem_long_batch below.
  * The seven arrays are malloc'd (never NULL on success; free with bwtmi_free):
  * smem_off[nq + 1]; qstart, qend, strand, count[*nsmem]; pos_off[*nsmem + 1];
  * pos[*npos]. */
@@ -349,6 +366,32 @@ int bwtmi_index_smem_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, 
                            int64_t **smem_off, int32_t **qstart, int32_t **qend, uint8_t **strand, int64_t **count,
                            int64_t **pos_off, int64_t **pos, int64_t *nsmem, int64_t *npos,
                            int64_t *positions_total, int64_t *work);
+/* The same search for long reads: the contract, arguments, outputs and errors
+ * of bwtmi_index_smem_batch, word for word, with 1 <= m <= 1,048,576; for any
+ * input that both entries accept the results are identical, `work` (still the
+ * sum of l(e), exact) included.  The index must have been built with
+ * BWTMI_INDEX_REVERSE, else BWTMI_E_STATE.  *steps (may be NULL) receives the
+ * rank steps really taken, summed over the searched strings; on any error it is
+ * 0 like the other counts (positions_total excepted, as above).
+ *   how      one lane per searched string walks its SMEMs left to right: from
+ *            a start i the match is extended rightwards to j = F(i) by plain
+ *            backward steps in the reverse index; then l(e) = e - i for every
+ *            end up to j, [i, j) is an SMEM (its SA interval comes from one
+ *            backward search of Q[i, j) in the forward index, skipped when
+ *            j - i < min_len), and the next start is s(j+1) = j + 1 - l(j+1),
+ *            from one backward search from end j + 1 in the forward index.
+ *   cost     about l(j+1) + 2 len rank steps per SMEM of len bytes: linear in m
+ *            for a read that matches the text in a few long stretches (a whole
+ *            3,000-byte text as its own query: 6,000 steps against work =
+ *            4.5 M).  Worst case: SMEMs that overlap almost completely -- a
+ *            read whose repeat tract is longer than the text's, "A" x 1600
+ *            against "A" x 1500: 101 SMEMs of 1500 bytes, 450,000 steps on one
+ *            lane -- are still m^2 / 2 and more, on a single lane. */
+int bwtmi_index_smem_long_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                                int32_t min_len, uint32_t flags, int64_t max_occ, int64_t max_positions,
+                                int64_t **smem_off, int32_t **qstart, int32_t **qend, uint8_t **strand,
+                                int64_t **count, int64_t **pos_off, int64_t **pos, int64_t *nsmem, int64_t *npos,
+                                int64_t *positions_total, int64_t *work, int64_t *steps);
 
 /* ------------------------------------------------------------ repeat job
  * Replaces the per-contig worker result handling and the post-processing of

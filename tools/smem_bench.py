@@ -20,7 +20,18 @@ package under --tree (default: this tree), so that two trees can be run
 alternately; prints one JSON line with the kernel times and a digest of the
 results.
 
-    python tools/smem_bench.py --untouched [--tree DIR]"""
+    python tools/smem_bench.py --untouched [--tree DIR]
+
+With --long: the long-read entry (BWTCore.smem_long_batch) on the
+same contig, one index built with its reverse index.  Three records: (1) the
+workload above through smem_batch and smem_long_batch in turn, equal digests
+asserted, each entry's wall time (min of 5, the two alternating) and kernel
+times; (2) 1,000 reads of 10 kbp cut from the contig with 1 % substitutions,
+half reverse-complemented, min_len 19, both strands, through smem_long_batch
+(smem_batch refuses them): wall time, the walk kernel's time, `steps`, `work`;
+(3) the wall time of the index build with and without the reverse index.
+
+    python tools/smem_bench.py --long OUT.json [--long-reads N] [--long-bp M]"""
 import argparse
 import hashlib
 import json
@@ -125,6 +136,79 @@ def smem_runs(ctx, n, nreads, m, nsub, min_len, route_seconds, reps=5):
     return run
 
 
+def _digest(got):
+    return hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in (
+        got.offsets, got.qstart, got.qend, got.strand, got.count, got.pos_offsets, got.positions))).hexdigest()[:16]
+
+
+def _timed(ctx, calls, reps=5):
+    """name -> (walls ms, kernel statistics of one more call, last result); the
+    calls alternate inside every repeat, after one warm call each."""
+    from bwtmi import _lib
+    out = {name: [[], None, None] for name in calls}
+    for name, call in calls.items():
+        call()
+    for _ in range(reps):
+        for name, call in calls.items():
+            t0 = time.perf_counter()
+            out[name][2] = call()
+            out[name][0].append(round((time.perf_counter() - t0) * 1e3, 3))
+    for name, call in calls.items():
+        _lib.kernel_stats(ctx, enable=True, reset=True)
+        call()
+        out[name][1] = _lib.kernel_stats(ctx, enable=False, reset=True)
+    return out
+
+
+def _entry_record(walls, ks, got, rank):
+    return dict(wall_ms=min(walls), wall_ms_repeats=walls, rank_kernel=rank, rank_kernel_ms=round(ks[rank][0], 4),
+                kernels_ms=round(sum(v[0] for v in ks.values()), 4), work=int(got.work), steps=int(got.steps),
+                smems=int(got.qstart.size), positions=int(got.positions.size), results_sha256=_digest(got),
+                kernels=_kern(ks))
+
+
+def long_runs(ctx, n, nreads, long_reads, long_bp):
+    from bwtmi import BWTCore
+    seq = _contig(n)
+    text = seq + b"$"
+    # (3) the build, with and without the reverse index, alternating
+    builds = {"forward_only": [], "with_reverse": []}
+    for rep in range(4):
+        for name, flag in (("forward_only", False), ("with_reverse", True)):
+            t0 = time.perf_counter()
+            core = BWTCore(text, build_kmer=False, reverse_index=flag)
+            if rep:      # (the first pair sizes the context's scratch)
+                builds[name].append(round((time.perf_counter() - t0) * 1e3, 2))
+            core.clear()
+    build = dict(bp=n, build_kmer=False, wall_ms_forward_only=min(builds["forward_only"]),
+                 wall_ms_with_reverse=min(builds["with_reverse"]), repeats=builds,
+                 ratio=round(min(builds["with_reverse"]) / min(builds["forward_only"]), 3))
+    core = BWTCore(text, build_kmer=False, reverse_index=True)
+    # (1) the short reads through both entries
+    reads = make_reads(seq, nreads, 150, 3)
+    t = _timed(ctx, {"smem_batch": lambda: core.smem_batch(reads, min_len=19, both_strands=True),
+                     "smem_long_batch": lambda: core.smem_long_batch(reads, min_len=19, both_strands=True)})
+    short = _entry_record(*t["smem_batch"], "k_smem_ms2")
+    long_ = _entry_record(*t["smem_long_batch"], "k_smem_walk2")
+    assert short["results_sha256"] == long_["results_sha256"] and short["work"] == long_["work"]
+    both = dict(bp=n, reads=nreads, read_bp=150, substitutions=3, min_len=19, both_strands=True,
+                smem_batch=short, smem_long_batch=long_,
+                wall_ratio_long_over_short=round(long_["wall_ms"] / short["wall_ms"], 3),
+                kernels_ratio_long_over_short=round(long_["kernels_ms"] / short["kernels_ms"], 3),
+                rank_kernel_ratio_long_over_short=round(long_["rank_kernel_ms"] / short["rank_kernel_ms"], 3))
+    # (2) long reads: the long entry alone
+    lreads = make_reads(seq, long_reads, long_bp, long_bp // 100, seed=9100)
+    t = _timed(ctx, {"smem_long_batch": lambda: core.smem_long_batch(lreads, min_len=19, both_strands=True)}, reps=3)
+    rec = _entry_record(*t["smem_long_batch"], "k_smem_walk2")
+    rec.update(bp=n, reads=long_reads, read_bp=long_bp, substitutions=long_bp // 100, min_len=19, both_strands=True,
+               lanes=2 * long_reads * long_bp, steps_per_work=round(rec["steps"] / rec["work"], 4),
+               steps_per_query_byte=round(rec["steps"] / (2 * long_reads * long_bp), 3),
+               walk_steps_per_ns=round(rec["steps"] / (rec["rank_kernel_ms"] * 1e6), 3),
+               smem_batch="refuses queries past 1024 bytes: no comparison exists")
+    core.clear()
+    return dict(short_reads_both_entries=both, long_reads=rec, index_build=build)
+
+
 def untouched(ctx, n=10_000_000):
     """The existing searches, from whichever tree `bwtmi` was imported from."""
     from bwtmi import BWTCore, MotifUtils, _lib
@@ -178,6 +262,9 @@ def main():
     ap.add_argument("out", nargs="?")
     ap.add_argument("--route-seconds", type=float, default=60.0)
     ap.add_argument("--untouched", action="store_true")
+    ap.add_argument("--long", action="store_true")
+    ap.add_argument("--long-reads", type=int, default=1000)
+    ap.add_argument("--long-bp", type=int, default=10_000)
     ap.add_argument("--tree", default=REPO)
     ap.add_argument("--bp", type=int, default=10_000_000)
     ap.add_argument("--reads", type=int, default=10_000)
@@ -188,6 +275,12 @@ def main():
     if a.untouched:
         print(json.dumps(dict(tree=os.path.abspath(a.tree), lib=_lib.source_hash()[:12], **untouched(ctx, a.bp))),
               flush=True)
+        return
+    if a.long:
+        runs = long_runs(ctx, a.bp, a.reads, a.long_reads, a.long_bp)
+        print(json.dumps(runs), flush=True)
+        with open(a.out, "w") as fh:
+            json.dump(dict(host=_lib.host_info(), **runs), fh, indent=1)
         return
     run = smem_runs(ctx, a.bp, a.reads, 150, 3, 19, a.route_seconds)
     print(json.dumps(run), flush=True)
