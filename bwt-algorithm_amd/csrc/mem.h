@@ -1,7 +1,7 @@
 // mem.h -- large host blocks for the per-step arrays of the host stages.
 //
 // A 100 Mbp step touches ~1 GB of fresh host arrays (downloaded hits, fold
-// items, speculative fold output, records, rendered rows).  Served by malloc,
+// items, fold output, records, rendered rows).  Served by malloc,
 // each step faults all of it in again 4 KiB at a time (measured: ~130-200k
 // minor faults per post-processing call, a large share of its wall time).
 // Blocks of >= kBigMin bytes therefore come from 2 MiB-aligned anonymous

@@ -5,9 +5,10 @@
 // equal (normally exactly one contig).  Every stage of the reference either
 // groups by chromosome or folds over the globally sorted list with a
 // same-chromosome test, so units are independent.  Inside a unit every stage
-// is either data-parallel (nested-suppression queries, refine, restore) or a
-// fold that is parallelised speculatively and then repaired to the exact
-// sequential result (merge), so the output does not depend on thread count.
+// is either data-parallel (nested-suppression queries) or part of the one
+// sequential fold-to-filter pass (fold_cuts), which runs in parallel over the
+// segments between verified cuts: each segment gets the exact sequential
+// result, so the output does not depend on thread count.
 //
 // Records travel as compact Items: a strict hit (bwt.py:1952-1993) is fully
 // determined by (start, end, motif length, copies) -- its motif is a slice of
@@ -16,7 +17,6 @@
 // always the current frame's slice [start, end) (trimmed before
 // _restore_reference_coordinates, full after), so it is never stored.
 #include <algorithm>
-#include <optional>
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -25,7 +25,6 @@
 #include <mutex>
 #include <cstdio>
 #include <cstdlib>
-#include <deque>
 #include <exception>
 #include <functional>
 #include <memory>
@@ -427,20 +426,6 @@ static void parallel_items(int64_t n, int nt, F &&fn) {
             if (k >= n) break;
             fn(k, w);
         }
-    };
-    if (nt == 1) { work(0); return; }
-    Pool::current().run(nt, work);
-}
-
-// static blocks: worker w takes items [n w / nt, n (w + 1) / nt) -- for the
-// memory-bound passes over the fold's chunks, so that a chunk is read by the
-// worker (and the core's cache) that wrote it in the pass before
-template <class F>
-static void parallel_blocks(int64_t n, int nt, F &&fn) {
-    if (n <= 0) return;
-    nt = (int)std::max<int64_t>(1, std::min<int64_t>(nt, n));
-    auto work = [&](int w) {
-        for (int64_t k = n * w / nt; k < n * (w + 1) / nt; ++k) fn(k, w);
     };
     if (nt == 1) { work(0); return; }
     Pool::current().run(nt, work);
@@ -1150,72 +1135,6 @@ bool try_merge(const UnitCtx &u, Pools &pools, int w, const Item &r1, Canon &c1,
     return true;
 }
 
-// Output of a speculative run, compactly: most records leave the fold
-// unchanged, so an emitted record is its index in R (>= 0), or ~k for side[k],
-// a merged record with the index of its run's first item.  The step at which
-// entry q was emitted is the first index of the next run (entry q + 1, or the
-// pending run).
-struct SpecOut {
-    struct Side {
-        int64_t j;
-        Item it;
-    };
-    std::vector<int64_t, BigAlloc<int64_t>> emitted;
-    std::vector<Side> side;
-    Item pending;
-    int64_t pending_j = 0;
-    Canon pending_canon;
-    int64_t start(size_t q) const {
-        if (q >= emitted.size()) return pending_j;
-        const int64_t e = emitted[q];
-        return e >= 0 ? e : side[(size_t)~e].j;
-    }
-    const Item &record(const ItemVec &R, size_t q) const {
-        const int64_t e = emitted[q];
-        return e >= 0 ? R[(size_t)e] : side[(size_t)~e].it;
-    }
-};
-
-// speculative run over [b, e): starts with cur = R[b] as if fresh at b
-void spec_run(const UnitCtx &u, Pools &pools, int w, const ItemVec &R, int64_t b, int64_t e,
-              std::vector<uint8_t, BigAlloc<uint8_t>> &fresh, SpecOut &o) {
-    Item cur = R[(size_t)b];
-    int64_t cur_j = b;
-    bool merged = false;
-    Canon cb[2];   // canonical forms of cur and of the next record; roles swap by index
-    int ci_cur = 0;
-    fresh[(size_t)b] = 1;
-    Item mg;
-    o.emitted.reserve((size_t)(e - b));
-    for (int64_t i = b + 1; i < e; ++i) {
-        Canon &cc = cb[ci_cur], &ci = cb[ci_cur ^ 1];
-        ci.ok = false;
-        if (stats_on(2)) (merged ? g_chain_tests : g_fresh_tests).fetch_add(1, std::memory_order_relaxed);
-        if (try_merge(u, pools, w, cur, cc, R[(size_t)i], ci, mg)) {
-            if (stats_on(2)) (merged ? g_chain_merges : g_fresh_merges).fetch_add(1, std::memory_order_relaxed);
-            cur = mg;
-            merged = true;
-            cc.ok = false;
-            fresh[(size_t)i] = 0;
-        } else {
-            if (merged) {
-                o.emitted.push_back(~(int64_t)o.side.size());
-                o.side.push_back({cur_j, cur});
-            } else {
-                o.emitted.push_back(cur_j);
-            }
-            cur = R[(size_t)i];
-            cur_j = i;
-            merged = false;
-            ci_cur ^= 1;
-            fresh[(size_t)i] = 1;
-        }
-    }
-    o.pending = cur;
-    o.pending_j = cur_j;
-    o.pending_canon = std::move(cb[ci_cur]);
-}
-
 // _refine_repeats (bwt.py:3291-3314) for one record: only recomputed records
 // can carry mismatches; a record whose recompute already covered exactly
 // [start, end) with this motif length would be recomputed with the same
@@ -1229,189 +1148,6 @@ inline void refine_one(const UnitCtx &u, Pools &pools, int w, Item &r) {
         m = std::max<int64_t>(1, (r.end - r.start) / std::max<int64_t>(1, rc ? rc : 1));
     }
     r = recompute(u, pools, w, r.chrom, r.start, r.end, m, tier_of(r), &r);
-}
-
-// the fold's output, refined (the refine pass runs inside the parallel
-// assembly: records are independent there)
-// chunks of the fold's output for the collapse pass: [cut[k], cut[k+1]) with
-// cmax[k] >= the largest end in it (exact unless an equal-start run was
-// reordered across the chunk's edge: then an upper bound, which only moves the
-// collapse's independent cuts later)
-struct OutChunks {
-    std::vector<int64_t> cut, cmax;
-};
-
-// fill (optional): writes R[a, b) -- the records are converted by the
-// speculative task that reads them first (device-screened hits), not by a pass
-// of their own
-ItemVec merge_fold(const UnitCtx &u0, Pools &pools, const ItemVec &R, int nt, OutChunks *oc = nullptr,
-                   const std::function<void(int64_t, int64_t)> *fill = nullptr) {
-    const int64_t n = (int64_t)R.size();
-    if (n == 0) return {};
-    const UnitCtx &u = u0;
-    const int64_t K = std::max<int64_t>(1, std::min<int64_t>((int64_t)nt * 8, n / 2048 + 1));
-    std::vector<int64_t> cut((size_t)K + 1);
-    for (int64_t k = 0; k <= K; ++k) cut[(size_t)k] = n * k / K;
-    std::vector<uint8_t, BigAlloc<uint8_t>> fresh((size_t)n, 0);
-    std::vector<SpecOut> spec((size_t)K);
-    auto ts0 = std::chrono::steady_clock::now();
-    std::vector<double> cms(stats_on() ? (size_t)K : 0);
-    // test hook: BWTMI_FAIL_MERGE_CHUNK=k throws inside worker task k (-2: the last
-    // task) -- the pool must hand the error back through the C ABI (tests/test_host.py)
-    const int64_t inj_k = knob(KN_FAIL_MERGE_CHUNK);
-    const int64_t inj = inj_k == -1 ? -1 : inj_k < 0 ? K - 1 : inj_k;
-    auto spec_task = [&](int64_t k, int w) {
-        if (k == inj) fail(BWTMI_E_STATE, "injected failure in merge task %lld", (long long)k);
-        auto a = std::chrono::steady_clock::now();
-        if (fill) (*fill)(cut[(size_t)k], cut[(size_t)k + 1]);
-        spec_run(u, pools, w, R, cut[(size_t)k], cut[(size_t)k + 1], fresh, spec[(size_t)k]);
-        if (stats_on()) cms[(size_t)k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
-    };
-    parallel_items(K, nt, spec_task);   // dynamic: the chunks' costs are uneven (r04ze: static blocks no better)
-    auto ts1 = std::chrono::steady_clock::now();
-    if (stats_on()) {
-        double sum = 0, mx = 0;
-        for (double v : cms) { sum += v; mx = std::max(mx, v); }
-        std::fprintf(stderr, "  merge spec %.1f ms (K=%lld, chunk sum %.1f max %.1f ms)\n",
-                     std::chrono::duration<double, std::milli>(ts1 - ts0).count(), (long long)K, sum, mx);
-    }
-    // repair: chunk 0 is exact; a later chunk's speculative results hold from
-    // the first index where the true run restarts (non-merge) at an index
-    // where the speculative run restarted too
-    // The serial part only walks each chunk up to its sync point; the output
-    // is then assembled in parallel: chunk k contributes rep[k] (records the
-    // true run emitted before syncing) and its speculative entries from[k] on.
-    std::vector<ItemVec> rep((size_t)K);
-    std::vector<size_t> from((size_t)K, 0);
-    std::vector<uint8_t> synced((size_t)K, 0);
-    synced[0] = 1;
-    Item cur = spec[0].pending;
-    Canon cb[2];
-    int ci_cur = 0;
-    cb[0] = std::move(spec[0].pending_canon);
-    Item mg;
-    for (int64_t k = 1; k < K; ++k) {
-        const int64_t b = cut[(size_t)k], e = cut[(size_t)k + 1];
-        SpecOut &sp = spec[(size_t)k];
-        int64_t sync = -1;
-        for (int64_t i = b; i < e; ++i) {
-            Canon &cc = cb[ci_cur], &ci = cb[ci_cur ^ 1];
-            ci.ok = false;
-            if (try_merge(u, pools, 0, cur, cc, R[(size_t)i], ci, mg)) {
-                cur = mg;
-                cc.ok = false;
-            } else {
-                rep[(size_t)k].push_back(cur);
-                cur = R[(size_t)i];
-                ci_cur ^= 1;
-                if (fresh[(size_t)i]) { sync = i; break; }
-            }
-        }
-        if (sync < 0) continue;   // never re-synchronised: `cur` carries into chunk k+1
-        size_t q = 0;             // the speculative entry of the run starting at sync
-        while (q < sp.emitted.size() && sp.start(q + 1) <= sync) ++q;
-        from[(size_t)k] = q;
-        synced[(size_t)k] = 1;
-        cur = sp.pending;
-        cb[ci_cur] = std::move(sp.pending_canon);
-    }
-    auto ts2 = std::chrono::steady_clock::now();
-    std::vector<size_t> at((size_t)K + 1, 0);
-    for (int64_t k = 0; k < K; ++k) {
-        const SpecOut &sp = spec[(size_t)k];
-        at[(size_t)k + 1] = at[(size_t)k] + rep[(size_t)k].size() +
-                            (synced[(size_t)k] ? sp.emitted.size() - from[(size_t)k] : 0);
-    }
-    ItemVec out(at[(size_t)K] + 1);
-    // assembly, refine, and the (start, end) order of the result: the fold's
-    // output is ordered by start (a merged record starts where its run did);
-    // refine only moves ends, so only runs of equal start need ordering by end
-    // -- done here per chunk, then for the runs that cross a chunk edge
-    std::vector<uint8_t> by_start((size_t)K, 1);
-    std::vector<int64_t> cm((size_t)K + 1, INT64_MIN);
-    auto by_end = [](const Item &x, const Item &y) { return x.end < y.end; };
-    // a chunk's largest end, its order check and its equal-start runs ordered by end
-    auto finish_chunk = [&](int64_t k) {
-        Item *const d0 = out.data() + at[(size_t)k], *const dst = out.data() + at[(size_t)k + 1];
-        int64_t mx = INT64_MIN;
-        for (Item *it = d0; it < dst; ++it) mx = std::max(mx, it->end);
-        cm[(size_t)k] = mx;
-        for (Item *it = d0 + 1; it < dst; ++it)
-            if (it[-1].start > it->start) { by_start[(size_t)k] = 0; return; }
-        for (Item *i = d0; i < dst;) {
-            Item *j = i + 1;
-            while (j < dst && j->start == i->start) ++j;
-            if (j - i > 1) std::stable_sort(i, j, by_end);
-            i = j;
-        }
-    };
-    // The imperfect records (the only ones refine recomputes) are few and
-    // clustered along the contig: refined inside the assembly, a chunk holding
-    // hundreds of them held its worker for milliseconds while the others idled
-    // (20 Mbp: 4.5k imperfect of 767k, 2.6k recomputes; the pass 3-6 ms, 1.5-2
-    // without them).  So the assembly copies and lists them, they are refined
-    // as one dynamic task list, and only the chunks holding them are finished
-    // after that.
-    std::vector<std::vector<int64_t>> imp((size_t)K);
-    parallel_items(K, nt, [&](int64_t k, int) {
-        const SpecOut &sp = spec[(size_t)k];
-        Item *const d0 = out.data() + at[(size_t)k];
-        Item *dst = d0;
-        const ItemVec &rp = rep[(size_t)k];
-        dst = std::copy(rp.begin(), rp.end(), dst);
-        if (synced[(size_t)k])
-            for (size_t q = from[(size_t)k]; q < sp.emitted.size(); ++q) *dst++ = sp.record(R, q);
-        for (Item *it = d0; it < dst; ++it)
-            if (it->imperfect()) imp[(size_t)k].push_back(it - out.data());
-        if (imp[(size_t)k].empty()) finish_chunk(k);
-    });
-    std::vector<int64_t> todo;
-    for (auto &v : imp) todo.insert(todo.end(), v.begin(), v.end());
-    if (!todo.empty()) {
-        constexpr int64_t kPer = 8;   // records per task
-        parallel_items(((int64_t)todo.size() + kPer - 1) / kPer, nt, [&](int64_t q, int w) {
-            const int64_t a = q * kPer, b = std::min<int64_t>((int64_t)todo.size(), a + kPer);
-            for (int64_t i = a; i < b; ++i) refine_one(u, pools, w, out[(size_t)todo[(size_t)i]]);
-        });
-        parallel_items(K, nt, [&](int64_t k, int) {
-            if (!imp[(size_t)k].empty()) finish_chunk(k);
-        });
-    }
-    out[at[(size_t)K]] = cur;
-    refine_one(u, pools, 0, out[at[(size_t)K]]);
-    cm[(size_t)K] = out[at[(size_t)K]].end;   // the last record is chunk K of its own
-    bool ordered = true;
-    for (int64_t k = 0; k < K; ++k) ordered = ordered && by_start[(size_t)k];
-    const size_t N = out.size();
-    for (int64_t k = 1; k <= K && ordered; ++k) {   // chunk edges (the last edge precedes `cur`)
-        const size_t b = at[(size_t)k];
-        if (b == 0 || b >= N) continue;
-        if (out[b - 1].start > out[b].start) { ordered = false; break; }
-        if (out[b - 1].start < out[b].start || out[b - 1].end <= out[b].end) continue;
-        size_t i = b - 1, j = b + 1;   // the equal-start run across the edge
-        while (i > 0 && out[i - 1].start == out[b].start) --i;
-        while (j < N && out[j].start == out[b].start) ++j;
-        std::stable_sort(out.begin() + (std::ptrdiff_t)i, out.begin() + (std::ptrdiff_t)j, by_end);
-        // the chunks the run touches share one bound
-        size_t k0 = (size_t)k, k1 = (size_t)k;
-        while (k0 > 0 && at[k0] > i) --k0;
-        while (k1 < (size_t)K && at[k1 + 1] < j) ++k1;
-        int64_t m = INT64_MIN;
-        for (size_t q = k0; q <= k1; ++q) m = std::max(m, cm[q]);
-        for (size_t q = k0; q <= k1; ++q) cm[q] = m;
-    }
-    if (!ordered) sort_by_pos(out, nt);   // not expected: the general stable sort
-    if (oc && ordered) {
-        oc->cut.assign(at.begin(), at.end());
-        oc->cut.push_back((int64_t)N);
-        oc->cmax.assign(cm.begin(), cm.end());
-    }
-    if (stats_on()) {
-        auto d = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        std::fprintf(stderr, "  merge: repair %.1f assemble %.1f ms\n", d(ts1, ts2),
-                     d(ts2, std::chrono::steady_clock::now()));
-    }
-    return out;
 }
 
 // bwt.py:3327-3354
@@ -1600,30 +1336,39 @@ void materialize(const UnitCtx &u, const Item &it, int64_t shift, Rec &r) {   //
 // verified cut; the tasks it ran through are folded again from there, serially
 // (reconcile below; rare: on a 200 kbp contig with 2 % substitutions one bit
 // in ~8000 fails, and only one at a task's edge costs anything).
+//
+// Every fold unit takes this pass.  The bound says nothing about a unit of
+// several contigs (their records interleave by position) or about records that
+// carry an Extra on input (Tier 3), and BWTMI_FOLD_CUTS=0 asks for the answer
+// without cuts: such a source has no bits, record 0 opens the one segment, and
+// that segment gets the reference's serial fold, refine, order, collapse and
+// filter on one thread.
 struct CutSrc {
-    const ScreenedVec *sh = nullptr;   // device-screened hits, or
-    const ItemVec *recs = nullptr;     // host-screened records and their bits
+    const ScreenedVec *sh = nullptr;   // device-screened hits (bits: use theirs), or
+    bool bits = true;
+    const ItemVec *recs = nullptr;     // gathered records and their bits (cut == nullptr: none)
     const uint8_t *cut = nullptr;
     int32_t chrom = 0;
     int64_t n = 0;
+    bool has_bits() const { return sh ? bits : cut != nullptr; }
     void wait(int64_t k) const {   // records [0, k) readable
         if (sh) sh->wait(std::min(k, n));
     }
-    bool get(int64_t k, Item &it) const {   // record k; true: a cut
+    bool get(int64_t k, Item &it) const {   // record k; true: a cut (record 0 always opens a segment)
         if (sh) {
             int64_t s0, len, prim;
             const bool c = sh->get(k, s0, len, prim);
             it = Item{s0, s0 + len, nullptr, chrom, (int32_t)prim};
-            return c || k == 0;   // (the screen may have dropped the hits before the first one)
+            return (c && bits) || k == 0;   // (the screen may have dropped the hits before the first one)
         }
         it = (*recs)[(size_t)k];
-        return cut[k] != 0;
+        return k == 0 || (cut && cut[k] != 0);
     }
 };
 
 // the cut bits of n strict hits in (start, end) order, at(k, s, e, m): the
 // largest reach per chunk in parallel, a prefix over the chunks, a sequential
-// prefix inside each chunk (the pattern of the collapse's `sb`)
+// prefix inside each chunk
 template <class At>
 std::vector<uint8_t> host_cuts(int64_t n, int64_t min_copies, bool unit1_maximal, int nt, At &&at) {
     std::vector<uint8_t> cut((size_t)n);
@@ -1675,15 +1420,23 @@ void check_device_cuts(const UnitCtx &u, const ScreenedVec &sh, int nt) {
 }
 
 // The fused pass.  Tasks are nominal chunks of records (BWTMI_FOLD_CHUNK
-// records each; 0: the merge fold's rule), claimed in ascending order; task k
-// owns the records from the first cut at or after its nominal start up to the
-// first cut at or after its nominal end (none in its range: nothing), and
-// waits for the download of those records only.
-void fold_cuts(const UnitCtx &u, Pools &pools, const CutSrc &src, int nt, int64_t shift, RecVec &out, double *ms) {
+// records each; 0: at most 8 tasks per thread and at least 2048 records each),
+// claimed in ascending order; task k owns the records from the first cut at or
+// after its nominal start up to the first cut at or after its nominal end
+// (none in its range: nothing), and waits for the download of those records
+// only.
+// `shift` is the unit's common trim offset, added when the survivors are
+// materialised: the (start, end) order is unchanged by it and collapse only
+// compares overlaps, lengths and motifs.  restore: the unit's contigs have
+// different trim offsets (one of them is <= 2 trim long, offset 0), so its
+// segment goes to full-sequence coordinates before the collapse, as in
+// bwt.py:3316-3325, and shift is 0; such a unit has several contigs, so no bits.
+void fold_cuts(UnitCtx u, Pools &pools, const CutSrc &src, int nt, int64_t shift, bool restore, RecVec &out, double *ms) {
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     const int64_t n = src.n;
     if (n == 0) return;
+    if (restore && (src.has_bits() || shift != 0)) fail(BWTMI_E_STATE, "cut bits or a common shift on a unit with several trim offsets");
     const int64_t chunk = std::max<int64_t>(0, knob(KN_FOLD_CHUNK));
     const int64_t K = chunk > 0 ? (n + chunk - 1) / chunk : std::max<int64_t>(1, std::min<int64_t>((int64_t)nt * 8, n / 2048 + 1));
     auto nom = [&](int64_t k) { return chunk > 0 ? std::min(n, k * chunk) : n * k / K; };
@@ -1719,6 +1472,15 @@ void fold_cuts(const UnitCtx &u, Pools &pools, const CutSrc &src, int nt, int64_
             // the fold's output is ordered by start and refine only moves ends:
             // equal-start runs go by end (any other disorder: the same stable sort)
             if (!std::is_sorted(seg.begin(), seg.end(), lt)) std::stable_sort(seg.begin(), seg.end(), lt);
+            if (restore) {   // the one segment: each record to its contig's full frame, ordered again (bwt.py:3316-3325, 3505)
+                for (Item &it : seg) {
+                    const int64_t off = u.job->contigs[(size_t)it.chrom].trim_left;
+                    it.start += off;
+                    it.end += off;
+                }
+                u.restored = true;   // motif_of and materialize read the full sequence from here on
+                std::stable_sort(seg.begin(), seg.end(), lt);
+            }
             folded += (int64_t)seg.size();
             auto emit = [&](const Item &x) {
                 ++collapsed;
@@ -1743,20 +1505,25 @@ void fold_cuts(const UnitCtx &u, Pools &pools, const CutSrc &src, int nt, int64_
         (void)src.get(i, cur);
         Canon cb[2];   // canonical forms of cur and of the next record; roles swap by index
         int ci_cur = 0;
+        bool merged = false;   // cur is the result of a merge (BWTMI_STATS=2 counts the steps by it)
         int64_t j = i + 1;
         for (; j < n; ++j) {
             if (j >= waited) src.wait(waited = std::min(n, j + 256));   // past the nominal end, up to the next cut
             const bool bit = src.get(j, r);
             Canon &cc = cb[ci_cur], &ci = cb[ci_cur ^ 1];
             ci.ok = false;
+            if (stats_on(2)) (merged ? g_chain_tests : g_fresh_tests).fetch_add(1, std::memory_order_relaxed);
             if (try_merge(u, pools, w, cur, cc, r, ci, mg)) {
+                if (stats_on(2)) (merged ? g_chain_merges : g_fresh_merges).fetch_add(1, std::memory_order_relaxed);
                 cur = mg;
+                merged = true;
                 cc.ok = false;
                 unverified += bit;
                 continue;
             }
             seg.push_back(cur);
             cur = r;
+            merged = false;
             ci_cur ^= 1;
             if (!bit) continue;
             refine_seg();
@@ -1876,21 +1643,19 @@ void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vecto
     auto t0 = clk::now();
     UnitCtx u{&job, job.params.min_copies};
     Pools pools(std::max(1, nt));
-    // one contig, strict hits only: the fold to the filter in one pass over cut
-    // segments (fold_cuts; BWTMI_FOLD_CUTS=0: the general path).  Units of
-    // several contigs and records that carry an Extra on input (Tier 3) stay on
-    // the general path: screen_reach bounds records built from one contig's
-    // strict hits only
+    // Every unit ends in fold_cuts, the fold to the filter in one pass.  Cut
+    // bits are used (BWTMI_FOLD_CUTS, default 1) where screen_reach bounds the
+    // records: one contig, strict hits only.  Anything else is one segment.
     const bool cuts_on = knob(KN_FOLD_CUTS) != 0 && chroms.size() == 1;
-    // 1. nested suppression per chromosome (bwt.py:3928), concatenated in
-    //    chromosome order, stable-sorted by (start, end).
-    //    Hits the device already screened (nested.hip) arrive kept, sorted and
-    //    deduplicated per chromosome; a one-chromosome unit then skips 1-2.
-    ItemVec recs;
-    bool presorted = chroms.size() == 1;
-    // one device-screened contig (the usual unit): its compact hits become
-    // records inside the merge fold's speculative tasks, chunk by chunk
-    std::function<void(int64_t, int64_t)> fill_fn;
+    // With one trim offset for the whole unit the records keep their trimmed
+    // coordinates to the end and the offset is added when they are materialised;
+    // with several, fold_cuts restores them before the collapse.
+    bool one_offset = true;
+    for (int32_t c : chroms) one_offset = one_offset && job.contigs[(size_t)c].trim_left == job.contigs[(size_t)chroms[0]].trim_left;
+    const int64_t shift = one_offset && !chroms.empty() ? job.contigs[(size_t)chroms[0]].trim_left : 0;
+    auto d = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    // one device-screened contig without Tier 3 records (the usual unit): the
+    // tasks of the pass read its compact hits, which never enter a shared array
     if (chroms.size() == 1) {
         const int32_t c = chroms[0];
         const bool scr = (size_t)c < job.screened.size() && job.screened[(size_t)c] && (size_t)c < shits.size();
@@ -1898,33 +1663,29 @@ void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vecto
         const bool t3 = mine && (size_t)c < job.t3.size() && !job.t3[(size_t)c].empty();
         if (scr && !t3) {
             const ScreenedVec &sh = shits[(size_t)c];
-            if (cuts_on) {   // the records never enter a shared array
-                if (knob(KN_DEVICE_CHECKS)) check_device_cuts(u, sh, nt);
-                CutSrc src;
-                src.sh = &sh;
-                src.chrom = c;
-                src.n = sh.size();
-                auto t1 = clk::now();
-                fold_cuts(u, pools, src, nt, job.contigs[(size_t)c].trim_left, out, ms);
-                ScreenedVec().swap(shits[(size_t)c]);
-                HitVec().swap(raw[(size_t)c]);
-                if (ms) ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
-                return;
-            }
-            recs.resize(sh.size());   // NoInit: filled by fill_fn
-            fill_fn = [&recs, &sh, c](int64_t a, int64_t b) {
-                sh.wait(b);   // the scan's download of these hits may still be landing
-                for (int64_t k = a; k < b; ++k) {
-                    int64_t s0, len, prim;
-                    sh.get(k, s0, len, prim);
-                    recs[(size_t)k] = Item{s0, s0 + len, nullptr, c, (int32_t)prim};
-                }
-            };
+            if (cuts_on && knob(KN_DEVICE_CHECKS)) check_device_cuts(u, sh, nt);
+            CutSrc src;
+            src.sh = &sh;
+            src.bits = cuts_on;
+            src.chrom = c;
+            src.n = sh.size();
+            auto t1 = clk::now();
+            fold_cuts(u, pools, src, nt, shift, false, out, ms);
+            ScreenedVec().swap(shits[(size_t)c]);
+            HitVec().swap(raw[(size_t)c]);
+            if (ms) ms[0] += d(t0, t1);
+            return;
         }
     }
+    // 1. nested suppression per chromosome (bwt.py:3928), concatenated in
+    //    chromosome order, stable-sorted by (start, end).
+    //    Hits the device already screened (nested.hip) arrive kept, sorted and
+    //    deduplicated per chromosome; a one-chromosome unit then skips the sort
+    //    and the dedup.
+    ItemVec recs;
+    bool presorted = chroms.size() == 1;
     bool strict_only = true;   // no input record carries an Extra
     for (int32_t c : chroms) {
-        if (fill_fn) break;   // the fused path above
         auto &h = raw[(size_t)c];
         const bool scr = (size_t)c < job.screened.size() && job.screened[(size_t)c];
         presorted = presorted && scr;
@@ -1967,182 +1728,26 @@ void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vecto
     // 2. dedup (bwt.py:3189-3220)
     if (!presorted) dedup_sorted(u, recs);
     auto t2 = clk::now();
-    if (cuts_on && !fill_fn && strict_only && !recs.empty()) {   // host-screened hits: their cut bits, then the one pass
-        const std::vector<uint8_t> cut =
-            host_cuts((int64_t)recs.size(), u.min_copies, false, nt, [&](int64_t k, int64_t &s, int64_t &e, int64_t &m) {
-                const Item &r = recs[(size_t)k];
-                s = r.start;
-                e = r.end;
-                m = r.mlen;
-            });
-        CutSrc src;
-        src.recs = &recs;
-        src.cut = cut.data();
-        src.chrom = chroms[0];
-        src.n = (int64_t)recs.size();
-        const auto t_bits = clk::now();
-        fold_cuts(u, pools, src, nt, job.contigs[(size_t)chroms[0]].trim_left, out, ms);
-        if (ms) {
-            ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
-            ms[1] += std::chrono::duration<double, std::milli>(t2 - t1).count();
-            ms[2] += std::chrono::duration<double, std::milli>(t_bits - t2).count();   // the cut bits
-        }
-        return;
-    }
-    // 3. merge adjacent (bwt.py:3222-3289)
-    OutChunks oc;
-    {
-        BWTMI_STAGE("bwtmi:merge");
-        recs = merge_fold(u, pools, recs, nt, &oc, fill_fn ? &fill_fn : nullptr);
-    }
-    if (fill_fn) {
-        ScreenedVec().swap(shits[(size_t)chroms[0]]);
-        HitVec().swap(raw[(size_t)chroms[0]]);
-    }
-    auto t3 = clk::now();
-    std::optional<StageRange> rf;
-    rf.emplace("bwtmi:refine..filter");
-    // 4. refine (bwt.py:3291-3314): done inside merge_fold's assembly
-    auto r1 = clk::now();   // merge_fold returns its records in (start, end) order
-    auto r2 = clk::now();
-    // 5. restore coordinates (bwt.py:3316-3325); actual_sequence is the frame slice.
-    //    With one trim offset for the whole unit the (start, end) order is unchanged.
-    //    Collapse only compares overlaps, lengths and motifs, all shift-invariant,
-    //    so one common offset is added when the records are materialised.
-    bool one_offset = true;
-    for (int32_t c : chroms) one_offset = one_offset && job.contigs[(size_t)c].trim_left == job.contigs[(size_t)chroms[0]].trim_left;
-    const int64_t shift = one_offset && !chroms.empty() ? job.contigs[(size_t)chroms[0]].trim_left : 0;
-    if (!one_offset)
-        parallel_for((int64_t)recs.size(), nt, [&](int64_t a, int64_t b) {
-            for (int64_t k = a; k < b; ++k) {
-                Item &r = recs[(size_t)k];
-                const int64_t off = job.contigs[(size_t)r.chrom].trim_left;
-                r.start += off;
-                r.end += off;
-            }
+    // 3. the cut bits of host-screened strict hits, then merge, refine, restore,
+    //    collapse and the final filter in the one pass
+    std::vector<uint8_t> cut;
+    if (cuts_on && strict_only)
+        cut = host_cuts((int64_t)recs.size(), u.min_copies, false, nt, [&](int64_t k, int64_t &s, int64_t &e, int64_t &m) {
+            const Item &r = recs[(size_t)k];
+            s = r.start;
+            e = r.end;
+            m = r.mlen;
         });
-    if (!one_offset) u.restored = true;
-    // 6. collapse (bwt.py:3499-3513)
-    if (!one_offset) sort_by_pos(recs, nt);
-    auto r3 = clk::now();
-    const size_t n_before_collapse = recs.size();
-    clk::time_point t_collapse;
-    // collapsed list as indices into recs (the slot takes the preferred record).
-    // The fold only ever compares with the last kept record, and a collapse
-    // needs an overlap, so an index whose start is >= every earlier end always
-    // starts fresh: chunks cut at such indices fold independently.  Each chunk
-    // then counts its records that pass the final filter (bwt.py:3940-3944),
-    // and every chunk materialises its passing records at its offset.
-    const double mc = (double)job.params.min_copies;
-    auto pass = [&](uint32_t i) { return copies_of(recs[i]) >= mc && recs[i].end - recs[i].start >= 6; };
-    size_t n_collapsed = 0;
-    {
-        const int64_t N = (int64_t)recs.size();
-        // nominal chunks and the largest end in each: the merge fold's output
-        // chunks (it tracked their ends while assembling), else one pass here
-        std::vector<int64_t> nom, cmax;
-        if (one_offset && !oc.cut.empty() && oc.cut.back() == N) {
-            nom = std::move(oc.cut);
-            cmax = std::move(oc.cmax);
-        } else {
-            const int C0 = N > 8192 ? 4 * std::max(1, nt) : 1;
-            nom.resize((size_t)C0 + 1);
-            for (int t = 0; t <= C0; ++t) nom[(size_t)t] = N * t / C0;
-            cmax.assign((size_t)C0, INT64_MIN);
-            parallel_items(C0, nt, [&](int64_t t, int) {
-                int64_t m = INT64_MIN;
-                for (int64_t k = nom[(size_t)t]; k < nom[(size_t)t + 1]; ++k) m = std::max(m, recs[(size_t)k].end);
-                cmax[(size_t)t] = m;
-            });
-        }
-        const int C = (int)cmax.size();
-        std::vector<int64_t> sb((size_t)C + 1, N);
-        std::vector<int64_t> pre((size_t)C, INT64_MIN);   // max end before nominal chunk t
-        for (int t = 1; t < C; ++t) pre[(size_t)t] = std::max(pre[(size_t)t - 1], cmax[(size_t)t - 1]);
-        sb[0] = 0;
-        parallel_blocks(C - 1, nt, [&](int64_t q, int) {
-            const int64_t t = q + 1;
-            int64_t i = nom[(size_t)t], m = pre[(size_t)t];
-            while (i < N && recs[(size_t)i].start < m) m = std::max(m, recs[(size_t)i++].end);
-            sb[(size_t)t] = i;
-        });
-        for (int t = 1; t <= C; ++t) sb[(size_t)t] = std::max(sb[(size_t)t], sb[(size_t)t - 1]);
-        std::vector<std::vector<uint32_t>> part((size_t)C);
-        std::vector<int64_t> cnt((size_t)C + 1, 0);
-        parallel_blocks(C, nt, [&](int64_t t, int) {
-            auto &pc = part[(size_t)t];
-            pc.reserve((size_t)(sb[(size_t)t + 1] - sb[(size_t)t]) + 1);   // nearly every record stays
-            int64_t c = 0;   // records passing the final filter, counted as each slot is settled
-            for (int64_t k = sb[(size_t)t]; k < sb[(size_t)t + 1]; ++k) {
-                if (!pc.empty() && should_collapse(u, recs[pc.back()], recs[(size_t)k])) {
-                    if (!prefer_first(u, recs[pc.back()], recs[(size_t)k])) pc.back() = (uint32_t)k;
-                } else {
-                    if (!pc.empty()) c += pass(pc.back());
-                    pc.push_back((uint32_t)k);
-                }
-            }
-            if (!pc.empty()) c += pass(pc.back());
-            cnt[(size_t)t + 1] = c;
-        });
-        for (int t = 0; t < C; ++t) {
-            cnt[(size_t)t + 1] += cnt[(size_t)t];
-            n_collapsed += part[(size_t)t].size();
-        }
-        t_collapse = clk::now();
-        {
-            DeferConstruct raw;   // constructed below, in parallel
-            out.resize((size_t)cnt[(size_t)C]);
-        }
-        // each chunk constructs its slots and materialises them in one pass (the
-        // record is still in cache).  Every slot is constructed whatever throws:
-        // a chunk whose materialize throws constructs the rest of its slots
-        // before it reports, and the chunks after it only construct theirs, so
-        // the vector's destructor never meets a raw slot.
-        static_assert(std::is_nothrow_default_constructible<Rec>::value, "Rec() must not throw");
-        std::atomic<bool> failed{false};
-        std::exception_ptr err;
-        std::mutex err_mu;
-        parallel_blocks(C, nt, [&](int64_t t, int) {
-            const int64_t q0 = cnt[(size_t)t], q1 = cnt[(size_t)t + 1];
-            int64_t o = q0;   // slots [q0, o) are constructed
-            if (!failed.load(std::memory_order_relaxed)) {
-                try {
-                    const std::vector<uint32_t> &pt = part[(size_t)t];
-                    for (size_t j = 0; j < pt.size(); ++j) {
-                        if (j + 8 < pt.size()) {   // the record data of a later slot (written by other workers)
-                            const Item &ahead = recs[pt[j + 8]];
-                            if (ahead.xp) __builtin_prefetch(ahead.x());
-                        }
-                        const uint32_t i = pt[j];
-                        if (pass(i)) {
-                            ::new ((void *)&out[(size_t)o]) Rec();
-                            ++o;
-                            materialize(u, recs[i], shift, out[(size_t)o - 1]);
-                        }
-                    }
-                } catch (...) {
-                    failed.store(true, std::memory_order_relaxed);
-                    std::lock_guard<std::mutex> lk(err_mu);
-                    if (!err) err = std::current_exception();
-                }
-            }
-            for (; o < q1; ++o) ::new ((void *)&out[(size_t)o]) Rec();
-        });
-        if (err) std::rethrow_exception(err);
-    }
-    auto t4 = clk::now();
-    rf.reset();
-    if (stats_on()) {
-        auto d = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        std::fprintf(stderr, "  merge %.1f (-> %zu) refine %.1f sort %.1f restore+sort %.1f collapse %.1f (%zu -> %zu) filter+mat %.1f ms\n",
-                     d(t2, t3), n_before_collapse, d(t3, r1), d(r1, r2), d(r2, r3), d(r3, t_collapse), n_before_collapse,
-                     n_collapsed, d(t_collapse, t4));
-    }
+    CutSrc src;
+    src.recs = &recs;
+    src.cut = cut.empty() ? nullptr : cut.data();
+    src.n = (int64_t)recs.size();
+    const auto t_bits = clk::now();
+    fold_cuts(u, pools, src, nt, shift, !one_offset, out, ms);
     if (ms) {
-        ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        ms[1] += std::chrono::duration<double, std::milli>(t2 - t1).count();
-        ms[2] += std::chrono::duration<double, std::milli>(t3 - t2).count();
-        ms[3] += std::chrono::duration<double, std::milli>(t4 - t3).count();
+        ms[0] += d(t0, t1);
+        ms[1] += d(t1, t2);
+        ms[2] += d(t2, t_bits);   // the cut bits
     }
 }
 

@@ -504,10 +504,11 @@ int bwtmi_wire_record_size(void);
 int64_t bwtmi_job_contig_error(const bwtmi_job *job, int32_t id, char *buf, int64_t cap);
 /* per-stage wall times (ms) of the last scan/postprocess/render calls.  The
  * post-processing fills slots 2..5: screen+sort, dedup, merge, refine..filter.
- * A unit that runs merge, refine, collapse and the final filter in one pass
- * (one contig of strict hits, BWTMI_FOLD_CUTS=1) reports that pass under
- * `merge` and the materialisation of the surviving records under
- * `refine..filter`. */
+ * Every fold unit runs merge, refine, collapse and the final filter in one
+ * pass (over the segments between verified cuts; a unit of several contigs, a
+ * contig with Tier 3 records, or any unit under BWTMI_FOLD_CUTS=0 is one
+ * segment): `merge` is that pass with its cut bits, `refine..filter` the
+ * materialisation of the surviving records. */
 int bwtmi_job_stage_ms(const bwtmi_job *job, double *out8);
 
 /* Shard layout over ranks (replaces the Pool over contigs, bwt.py:3850-3912):

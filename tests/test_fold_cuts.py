@@ -1,12 +1,15 @@
 """The fold, refine, collapse and filter in one pass over cut segments (CPU).
 
-A unit of one contig whose input records are all strict hits takes
-post.cpp's fold_cuts (BWTMI_FOLD_CUTS=1, the default); BWTMI_FOLD_CUTS=0
-selects the general path (speculative fold, repair, assembly, collapse).  Every
-case asserts that the rendered strfinder text is the same, byte for byte.
-BWTMI_FOLD_CHUNK sets the records per task: at 1, 2 and 8 cuts and task edges
-fall everywhere and some tasks own nothing.
+Every fold unit takes post.cpp's fold_cuts.  A unit of one contig whose input
+records are all strict hits is folded segment by segment between verified cuts
+(BWTMI_FOLD_CUTS=1, the default); with BWTMI_FOLD_CUTS=0 no cut is used and the
+unit is one segment, the reference's serial fold -- which is also what a unit
+of several contigs gets whatever the switch.  Every case asserts that the
+rendered text is the same, byte for byte.  BWTMI_FOLD_CHUNK sets the records
+per task: at 1, 2 and 8 cuts and task edges fall everywhere and some tasks own
+nothing.
 """
+import ctypes
 import json
 import os
 
@@ -62,7 +65,7 @@ def test_gap_profile_contig(built_lib):
 
 
 def test_the_pass_reports_its_stages_and_verifies_its_cuts(built_lib, capfd):
-    """BWTMI_STATS=1 on the new path: the stage line (it names merge and collapse)
+    """BWTMI_STATS=1: the stage line (it names merge and collapse)
     counts hits, verified cuts and the bits that did not verify.  A cut is used
     only after it is verified on the records themselves, so a bit that the reach
     bound gets wrong changes nothing: with 2 % substitutions some bits do fail
@@ -82,7 +85,8 @@ def test_the_pass_reports_its_stages_and_verifies_its_cuts(built_lib, capfd):
     with _lib.knobs(FOLD_CUTS=0, STATS=1):
         want = _render(seq, hits, 3, 4)
     err = capfd.readouterr().err
-    assert "repair" in err and "one pass" not in err, err[-600:]
+    assert "one pass" in err and "repair" not in err, err[-600:]
+    assert "hits, 1 cuts (0 bits unverified, 0 tasks folded again)" in err, err[-600:]
     assert got == want
     # every task edge on an unverified bit's neighbourhood: chunks of 1 record
     with _lib.knobs(FOLD_CUTS=1, FOLD_CHUNK=1, STATS=1):
@@ -187,3 +191,71 @@ def test_injected_task_failure_comes_back_as_an_error(built_lib, task):
         assert _render(seq, hits, 3, 4) == want
     with _lib.knobs(FOLD_CUTS=0):
         assert _render(seq, hits, 3, 4) == want
+
+
+# chr01 / CHR1 / chr1 share a natural sort key: one fold unit of three contigs.
+# chr1 is 54 bp, at most twice the trim, so its trim offset is 0 and the others'
+# is 30; chr2 is a unit of its own.
+COLLIDING = ("chr01", "CHR1", "chr1")
+
+
+def write_colliding_fasta(path):
+    from bwtmi import synth
+    a = synth.generate_contig(24_000, 71, 0.03).decode()
+    b = synth.generate_contig(14_000, 72, 0.0).decode()
+    c = "TG" + "CAG" * 9 + "ACACACACACAC" + "AAAAAAAAAT" + "GTC"
+    assert len(c) == 54
+    with open(path, "w") as f:
+        for name, s in (("chr01", a), ("chr2", b[:9000]), ("CHR1", b), ("chr1", c)):
+            f.write(f">{name}\n")
+            for i in range(0, len(s), 60):
+                f.write(s[i:i + 60] + "\n")
+
+
+@pytest.fixture(scope="module")
+def colliding(tmp_path_factory, built_lib):
+    """The FASTA and the reference post-processing's bed and vcf text for it."""
+    from oracle import post
+    fa = str(tmp_path_factory.mktemp("unit") / "colliding.fa")
+    write_colliding_fasta(fa)
+    return fa, {fmt: post.run_file(fa, fmt) for fmt in ("bed", "vcf")}
+
+
+def _colliding_job(fa, threads):
+    from bwtmi import _lib
+    from test_host import _native_job
+    j = _native_job(fa, dict(fmt="bed", mc=3, trim=30, tier2=True))
+    j.params.threads = threads
+    _lib.check(_lib.lib().bwtmi_job_set_params(j.h, ctypes.byref(j.params)))
+    return j
+
+
+def test_unit_of_three_contigs_with_two_trim_offsets(colliding):
+    """Fold and refine in the trimmed frame, each record to its own contig's full
+    frame, then order, collapse and filter -- in the one segment such a unit is."""
+    from bwtmi import _lib
+    fa, want = colliding
+    rows = want["bed"].splitlines()
+    for name in COLLIDING:
+        assert sum(r.startswith(name + "\t") for r in rows) >= 1, name
+    for cuts in (0, 1):
+        for chunk in (0, 1, 8):
+            for threads in (1, 4):
+                with _lib.knobs(FOLD_CUTS=cuts, FOLD_CHUNK=chunk):
+                    j = _colliding_job(fa, threads)
+                    j.postprocess()
+                    for fmt in ("bed", "vcf"):
+                        assert j.render(fmt).decode() == want[fmt], (cuts, chunk, threads, fmt)
+
+
+@pytest.mark.parametrize("task", [0, -2])
+def test_injected_task_failure_in_a_unit_of_several_contigs(colliding, task):
+    from bwtmi import _lib
+    fa, want = colliding
+    with _lib.knobs(FAIL_MERGE_CHUNK=task):
+        j = _colliding_job(fa, 4)
+        with pytest.raises(_lib.BwtmiError, match="injected failure"):
+            j.postprocess()
+    j = _colliding_job(fa, 4)
+    j.postprocess()
+    assert j.render("bed").decode() == want["bed"]

@@ -1,9 +1,9 @@
 """The cut bit of the device screen (nested.hip) and the one pass over cut
 segments that reads it (post.cpp fold_cuts): with BWTMI_FOLD_CUTS=1 (the
 default) a device-screened contig gives the same records as with
-BWTMI_FOLD_CUTS=0 (the general path), whatever the screen's other switches,
-in both download layouts, and the device's bits are the host's
-(BWTMI_DEVICE_CHECKS=1)."""
+BWTMI_FOLD_CUTS=0 (the same pass with the bits ignored: one segment, the serial
+fold), whatever the screen's other switches, in both download layouts, and the
+device's bits are the host's (BWTMI_DEVICE_CHECKS=1)."""
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,7 @@ def contigs():
 
 @pytest.fixture(scope="module")
 def general_path(gpu_ctx, contigs):
-    """The records of the general path (FOLD_CUTS=0), computed once."""
+    """The records without cuts (FOLD_CUTS=0: one segment), computed once."""
     from bwtmi import _lib
     with _lib.knobs(FOLD_CUTS=0):
         return {k: _scan_render(v) for k, v in contigs.items()}
@@ -86,3 +86,26 @@ def test_c4_shape_several_one_contig_units(gpu_ctx):
         with _lib.knobs(FOLD_CUTS=cuts):
             out.append(_scan_render(cs))
     assert out[0] == out[1] and out[0].count(b"\n") > 1000
+
+
+def test_unit_of_device_screened_contigs_with_two_trim_offsets(gpu_ctx, tmp_path):
+    """chr01 / CHR1 / chr1 in one fold unit (chr1 at offset 0) next to chr2, a unit
+    of its own, through the device scan and screen: the unit of several screened
+    contigs, and with FOLD_CUTS=0 chr2's screened hits with their bits ignored,
+    against the reference post-processing."""
+    from oracle import post
+    from bwtmi import TandemRepeatFinder, _lib
+    from test_fold_cuts import COLLIDING, write_colliding_fasta
+    fa = str(tmp_path / "colliding.fa")
+    write_colliding_fasta(fa)
+    want = post.run_file(fa, "bed")
+    for name in COLLIDING + ("chr2",):
+        assert "\n" + name + "\t" in "\n" + want, name
+    for cuts in (0, 1):
+        with _lib.knobs(FOLD_CUTS=cuts):
+            f = TandemRepeatFinder(fa)
+            f.load_reference()
+            reps = f.find_tandem_repeats_parallel()
+            out = tmp_path / f"cuts{cuts}.bed"
+            f.save_results(reps, str(out), "bed")
+        assert out.read_text() == want, cuts
