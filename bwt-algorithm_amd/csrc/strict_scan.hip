@@ -9,10 +9,18 @@
 // Kernel pipeline (one launch each, all on the ctx stream):
 //   k_pack       bytes -> B-bit codes (B = 2/4/8 from the contig's alphabet),
 //                64-bit words, coalesced
-//   k_runs       grid (word tiles x L chunks): every lane owns 32 positions
-//                for every L of its chunk; equality masks by XOR of packed windows, neighbour
-//                masks by wave shuffles; emits the maximal runs long enough
-//                to hold min_copies copies (candidates)
+//   k_runs       the dense kernel (unit lengths whose qualifying runs may be
+//                shorter than 95 positions).  Grid (word tiles x L chunks):
+//                every lane owns 32 positions for every L of its chunk;
+//                equality masks by XOR of packed windows, neighbour masks by
+//                wave shuffles; emits the maximal runs long enough to hold
+//                min_copies copies (candidates)
+//   k_runs_tiled, k_runs_sparse   the sampled kernels (all longer unit
+//                lengths: every s-th word).  One body, sampled_runs, over two
+//                word sources: an LDS tile of the planes or, when a launch's
+//                largest stride or tile does not fit, the global planes
+//   k_streak_end the streaks whose end lies more than one 64-word step
+//                (streak_end_step) past their owner, deferred by all three
 //   radix sort   candidates by (L desc, s asc) -- the reference order
 //   k_resolve    chains of candidates closer than L (where carry can act) are
 //                walked by their head lane; all others resolve independently
@@ -21,8 +29,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
-#include <cstring>
+#include <numeric>
+#include <type_traits>
 #include <vector>
 
 #include "device.h"
@@ -73,21 +81,64 @@ __global__ __launch_bounds__(256) void k_pack(const uint8_t *__restrict__ text, 
     for (int p = 0; p < B; ++p) P[w * B + p] = pl[p];
 }
 
-// M_L for positions 32w .. 32w+31 (bit k <-> position 32w+k), from global planes
+// The window mask: word a against the window that starts r bits into lo:hi
+// (bit k set <-> the codes at bits k and k + r of the two are equal), of which
+// only the low `lim` positions exist in the text (lim = n - L - 32w; 32: all)
 template <int B>
-__device__ __forceinline__ uint32_t eq32(const uint32_t *__restrict__ P, int64_t w, int64_t L, int64_t n) {
-    const int64_t j0 = w * 32;
-    const int64_t lim = n - L - j0;  // positions j0+k valid iff k < lim
-    if (w < 0 || lim <= 0) return 0u;
-    const int64_t q = w + (L >> 5);
-    const uint32_t r = (uint32_t)(L & 31);
+__device__ __forceinline__ uint32_t window_mask(const uint32_t (&a)[B], const uint32_t (&lo)[B],
+                                                const uint32_t (&hi)[B], uint32_t r, int64_t lim) {
     uint32_t x = 0;
 #pragma unroll
-    for (int p = 0; p < B; ++p)
-        x |= P[w * B + p] ^ __builtin_amdgcn_alignbit(P[(q + 1) * B + p], P[q * B + p], r);
-    uint32_t m = ~x;
-    if (lim < 32) m &= (1u << lim) - 1u;
-    return m;
+    for (int p = 0; p < B; ++p) x |= a[p] ^ __builtin_amdgcn_alignbit(hi[p], lo[p], r);
+    return lim <= 0 ? 0u : (lim < 32 ? ~x & ((1u << lim) - 1u) : ~x);
+}
+
+// M_L for positions 32w .. 32w+31 (bit k <-> position 32w+k), from planes W
+// whose first word is word `base` of the text; 0 before and past the text
+template <int B>
+__device__ __forceinline__ uint32_t eq32(const uint32_t *__restrict__ W, int64_t base, int64_t w, int64_t L,
+                                         int64_t n) {
+    const int64_t lim = n - L - w * 32;  // positions 32w+k valid iff k < lim
+    if (w < 0 || lim <= 0) return 0u;
+    const int64_t ia = (w - base) * B, iq = ia + (L >> 5) * B;   // words w and q = w + L / 32
+    uint32_t a[B], lo[B], hi[B];
+#pragma unroll
+    for (int p = 0; p < B; ++p) {
+        a[p] = W[ia + p];
+        lo[p] = W[iq + p];
+        hi[p] = W[iq + B + p];
+    }
+    return window_mask<B>(a, lo, hi, (uint32_t)(L & 31), lim);
+}
+
+// The two places a sampled kernel reads words from, with one interface:
+// planes(w, v) = the B planes of word w, eq(w, L) = M_L of word w.
+template <int B>
+struct PlaneWords {   // the global planes: zero outside [0, nwords32 + 8) (8 words of zero padding)
+    const uint32_t *__restrict__ P;
+    int64_t n, nwords32;
+    __device__ __forceinline__ void planes(int64_t w, uint32_t (&v)[B]) const {
+        const bool in = w >= 0 && w < nwords32 + 8;
+#pragma unroll
+        for (int p = 0; p < B; ++p) v[p] = in ? P[w * B + p] : 0u;
+    }
+    __device__ __forceinline__ uint32_t eq(int64_t w, int64_t L) const { return eq32<B>(P, 0, w, L, n); }
+};
+template <int B>
+struct TileWords {   // an LDS tile that holds words base .. of the planes (zero-filled outside them)
+    const uint32_t *tl;
+    int64_t base, n;
+    __device__ __forceinline__ void planes(int64_t w, uint32_t (&v)[B]) const {
+#pragma unroll
+        for (int p = 0; p < B; ++p) v[p] = tl[(w - base) * B + p];
+    }
+    __device__ __forceinline__ uint32_t eq(int64_t w, int64_t L) const { return eq32<B>(tl, base, w, L, n); }
+};
+
+// a 64-bit value of lane src (src wave-uniform): a scalar
+__device__ __forceinline__ int64_t readlane64(int64_t v, int src) {
+    return (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src) |
+           ((int64_t)__builtin_amdgcn_readlane((int)(v >> 32), src) << 32);
 }
 
 // Candidates go to kCandSegs segments of seg_cap slots, each with its own
@@ -130,6 +181,18 @@ __device__ __forceinline__ void put(const CandOut &o, int seg, unsigned long lon
         o.keys[at] = ((uint64_t)(o.umax - L) << o.sb) | (uint64_t)s;
         o.vals[at] = (uint64_t)e;
     }
+}
+
+// End of a streak (a run of full words) whose scan resumes at word q0, one
+// 64-word step: lane l holds Mq = M_L of word q0 + l.  The first non-full word
+// ends the streak at its first zero bit (M_L is 0 past the text: the scan ends
+// there); -1 when all 64 are full.  Every lane of the wave calls it; the result
+// is a scalar (ballot, readlane).
+__device__ __forceinline__ int64_t streak_end_step(uint32_t Mq, int64_t q0) {
+    const uint64_t nb = __ballot(Mq != FULL);
+    const int f = nb ? __ffsll((unsigned long long)nb) - 1 : 0;
+    const uint32_t Mf = (uint32_t)__builtin_amdgcn_readlane((int)Mq, f);
+    return nb ? (q0 + f) * 32 + (int64_t)__ffs(~Mf) - 1 : -1;
 }
 
 // segments -> one contiguous array (segment order)
@@ -190,7 +253,7 @@ __global__ __launch_bounds__(256) void k_runs(const uint32_t *__restrict__ P, in
     int64_t K = (mc - 1) * (Lg + r_lo);
     for (int r = r_lo; r <= r_hi; ++r, K += mc - 1) {
         const int64_t L = Lg + r;
-        uint32_t x = 0;
+        uint32_t x = 0;   // window_mask by hand, the clamp under `tail`: through the helper the kernel ran 1-3 % slower
 #pragma unroll
         for (int p = 0; p < B; ++p) x |= a[p] ^ __builtin_amdgcn_alignbit(hi[p], lo[p], (uint32_t)r);
         uint32_t M = ~x;
@@ -244,14 +307,10 @@ __global__ __launch_bounds__(256) void k_runs(const uint32_t *__restrict__ P, in
                 // N run is one for every unit length) is ended by k_streak_end, so
                 // the unit lengths' walks do not chain through this wave
                 const int64_t q0 = wave_base + 63;
-                const uint32_t Mq = eq32<B>(P, q0 + lane, L, n);   // 0 past the text: ends the scan
-                const uint64_t nb = __ballot(Mq != FULL);
-                if (nb) {
-                    const int f = __ffsll((unsigned long long)nb) - 1;
-                    const uint32_t Mf = (uint32_t)__shfl((int)Mq, f, 64);
-                    if (beyond) e_streak = (q0 + f) * 32 + (int64_t)__ffs(~Mf) - 1;
-                } else if (beyond) {
-                    push_pending(out, L, j0 - (int64_t)__clz(~Mp), q0 + 64);
+                const int64_t e = streak_end_step(eq32<B>(P, 0, q0 + lane, L, n), q0);
+                if (beyond) {
+                    if (e >= 0) e_streak = e;
+                    else push_pending(out, L, j0 - (int64_t)__clz(~Mp), q0 + 64);
                 }
             }
         }
@@ -742,6 +801,48 @@ struct SparseGroups {
     int64_t woff[kSparseMax + 1];    // first wave of each group in the launch
 };
 
+// What both sampled kernels do with a lane's sample: word w of stride s, its
+// mask M = M_L (0 on a lane without a sample or outside the unit lengths asked
+// for).  Every lane of the wave calls it; w, s and L may differ between lanes.
+// `words` answers the owner test, whose s words the kernel guarantees to hold;
+// the end step reads the global planes P (it may leave a tile).
+template <int B, class Words>
+__device__ __forceinline__ void sampled_runs(const Words &words, const uint32_t *__restrict__ P, int64_t n,
+                                             int64_t mc, int64_t w, int32_t s, int64_t L, uint32_t M, int seg,
+                                             const CandOut &out) {
+    // owner test, every full lane at once: the first non-full word among
+    // w-1 .. w-s gives the run's start (word w-s is the previous sample: all
+    // s full means that sample's run, not ours).  Inside a long streak every
+    // sample is full, so the s words are checked 8 loads at a time per lane
+    // rather than one lane after another for the whole wave.
+    int64_t start = -1;
+    if (__any(M == FULL) && M == FULL) {
+        for (int32_t k0 = 1; k0 <= s && start < 0; k0 += 8) {
+            uint32_t Mq[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) Mq[i] = k0 + i <= s ? words.eq(w - (k0 + i), L) : FULL;   // 0 before the text
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (start < 0 && Mq[i] != FULL) start = (w - (k0 + i) + 1) * 32 - (int64_t)__clz(~Mq[i]);
+        }
+    }
+    uint64_t own = __ballot(start >= 0);   // uniform
+    while (own) {   // one owner at a time, its word, start and L as scalars
+        const int src = __ffsll((unsigned long long)own) - 1;
+        own &= own - 1;
+        const int64_t ws = readlane64(w, src), st = readlane64(start, src), Lo = __builtin_amdgcn_readlane((int)L, src);
+        // end: the first non-full word after ws -- one 64-word step here, a
+        // longer streak is ended by k_streak_end
+        const int64_t end = streak_end_step(eq32<B>(P, 0, ws + 1 + (threadIdx.x & 63), Lo, n), ws + 1);
+        if ((threadIdx.x & 63) == 0) {
+            if (end < 0) push_pending(out, Lo, st, ws + 65);
+            else if (end - st >= (mc - 1) * Lo) put(out, seg, atomicAdd(out.count + seg, 1ull), Lo, st, end);
+        }
+    }
+}
+
+// The sampled groups straight from the global planes: a wave takes 64
+// consecutive samples of one group, the group's unit lengths in turn.
 template <int B>
 __global__ __launch_bounds__(256) void k_runs_sparse(const uint32_t *__restrict__ P, int64_t n, int64_t nwords32,
                                                      int32_t lmin, int32_t lmax, int64_t mc, SparseGroups sg,
@@ -751,74 +852,24 @@ __global__ __launch_bounds__(256) void k_runs_sparse(const uint32_t *__restrict_
     int gi = 0;
     while (gi + 1 < sg.ng && q >= sg.woff[gi + 1]) ++gi;   // uniform
     if (q >= sg.woff[sg.ng]) return;
-    const int64_t g = sg.g[gi], s = sg.s[gi];
+    const int32_t g = sg.g[gi], s = sg.s[gi];
     const int64_t w = ((q - sg.woff[gi]) * 64 + lane) * s;   // this lane's sampled word
     const bool inb = w < nwords32;
-    auto word = [&](int64_t x, int p) { return inb && x < nwords32 + 8 ? P[x * B + p] : 0u; };
+    const PlaneWords<B> words{P, n, nwords32};
     uint32_t a[B], lo[B], hi[B];
-#pragma unroll
-    for (int p = 0; p < B; ++p) {
-        a[p] = inb ? P[w * B + p] : 0u;
-        lo[p] = word(w + g, p);
-        hi[p] = word(w + g + 1, p);
-    }
-    const int64_t Lg = g * 32;
+    words.planes(w, a);
+    words.planes(w + g, lo);
+    words.planes(w + g + 1, hi);
+    const int64_t Lg = (int64_t)g * 32;
     const int r_lo = (int)max((int64_t)0, (int64_t)lmin - Lg);
     const int r_hi = (int)min((int64_t)31, (int64_t)lmax - Lg);
-    const int64_t j0 = w * 32;
-    const bool tail = !inb || j0 + 32 + Lg + 31 >= n;
+    const bool tail = !inb || w * 32 + 32 + Lg + 31 >= n;   // only the text's last words need the clamp
     const int seg = (int)(blockIdx.x & (kCandSegs - 1));
     for (int r = r_lo; r <= r_hi; ++r) {
-        const int64_t L = Lg + r, K = (mc - 1) * L;
-        uint32_t x = 0;
-#pragma unroll
-        for (int p = 0; p < B; ++p) x |= a[p] ^ __builtin_amdgcn_alignbit(hi[p], lo[p], (uint32_t)r);
-        uint32_t M = ~x;
-        if (tail) {
-            const int64_t lim = n - L - j0;
-            if (!inb || lim <= 0) M = 0u;
-            else if (lim < 32) M &= (1u << lim) - 1u;
-        }
-        // owner test, every full lane at once: the first non-full word among
-        // w-1 .. w-s gives the run's start (word w-s is the previous sample: all
-        // s full means that sample's run, not ours).  Inside a long streak every
-        // sample is full, so the s words are checked 8 loads at a time per lane
-        // rather than one lane after another for the whole wave.
-        int64_t start = -1;
-        if (__any(M == FULL) && M == FULL) {
-            for (int64_t k0 = 1; k0 <= s && start < 0; k0 += 8) {
-                uint32_t Mq[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) Mq[i] = k0 + i <= s ? eq32<B>(P, w - (k0 + i), L, n) : FULL;   // 0 before the text
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (start < 0 && Mq[i] != FULL) start = (w - (k0 + i) + 1) * 32 - (int64_t)__clz(~Mq[i]);
-            }
-        }
-        uint64_t own = __ballot(start >= 0);   // uniform
-        while (own) {
-            const int src = __ffsll((unsigned long long)own) - 1;
-            own &= own - 1;
-            const int64_t ws = (int64_t)__builtin_amdgcn_readlane((int)(w / s), src) * s;   // the owner's word
-            const int64_t st = ((int64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)start, src)) |
-                               ((int64_t)__builtin_amdgcn_readlane((int)(start >> 32), src) << 32);
-            // end: the first non-full word after ws -- one 64-word step here, a
-            // longer streak is ended by k_streak_end
-            const int64_t q0 = ws + 1;
-            const uint32_t Mq = eq32<B>(P, q0 + lane, L, n);   // 0 past the text: ends the scan
-            const uint64_t nb = __ballot(Mq != FULL);
-            if (!nb) {
-                if (lane == 0) push_pending(out, L, st, q0 + 64);
-                continue;
-            }
-            const int f = __ffsll((unsigned long long)nb) - 1;
-            const uint32_t Mf = (uint32_t)__builtin_amdgcn_readlane((int)Mq, f);
-            const int64_t end = (q0 + f) * 32 + (int64_t)__ffs(~Mf) - 1;
-            if (end - st >= K && lane == 0) {
-                const unsigned long long at = atomicAdd(out.count + seg, 1ull);
-                put(out, seg, at, L, st, end);
-            }
-        }
+        const int64_t L = Lg + r;
+        uint32_t M = window_mask<B>(a, lo, hi, (uint32_t)r, 32);
+        if (tail) M = inb ? window_mask<B>(a, lo, hi, (uint32_t)r, n - L - w * 32) : 0u;
+        sampled_runs<B>(words, P, n, mc, w, s, L, M, seg, out);
     }
 }
 
@@ -829,7 +880,7 @@ __global__ __launch_bounds__(256) void k_runs_sparse(const uint32_t *__restrict_
 // launch inside the tile from there -- the planes are read once per launch
 // instead of three scattered lines per sample and group.  Samples of all
 // groups are flattened over the lanes (the large-stride groups have few).
-// Candidates and their order-free output are exactly k_runs_sparse's.
+// What happens to a sample is k_runs_sparse's: both call sampled_runs.
 template <int B>
 constexpr int run_tile() { return 2048 / B; }   // words per workgroup: <= 64 KB of LDS with a 256-word halo
 constexpr int kRunGroupSplit = 2;   // gridDim.y: workgroups share a tile's groups (gi mod 2): 2x the
@@ -859,21 +910,7 @@ __global__ __launch_bounds__(256) void k_runs_tiled(const uint32_t *__restrict__
         }
     }
     __syncthreads();
-    // M_L of word w (bit k <-> position 32w + k), from the tile
-    auto eqL = [&](int64_t w, int64_t L) -> uint32_t {
-        const int64_t lim = n - L - w * 32;   // positions 32w + k valid iff k < lim
-        if (w < 0 || lim <= 0) return 0u;
-        const int64_t q = w + (L >> 5) - base;
-        const uint32_t r = (uint32_t)(L & 31);
-        const int64_t a = (w - base) * B;
-        uint32_t x = 0;
-#pragma unroll
-        for (int p = 0; p < B; ++p) x |= tl[a + p] ^ __builtin_amdgcn_alignbit(tl[(q + 1) * B + p], tl[q * B + p], r);
-        uint32_t m = ~x;
-        if (lim < 32) m &= (1u << lim) - 1u;
-        return m;
-    };
-    const int lane = threadIdx.x & 63;
+    const TileWords<B> words{tl, base, n};
     const int seg = (int)((blockIdx.x * gridDim.y + blockIdx.y) & (kCandSegs - 1));
     const int64_t total = pre[sg.ng];
     for (int64_t f0 = 0; f0 < total; f0 += 256) {   // uniform
@@ -881,71 +918,20 @@ __global__ __launch_bounds__(256) void k_runs_tiled(const uint32_t *__restrict__
         const bool live = f < total;
         int gi = 0;
         while (gi + 1 < sg.ng && f >= pre[gi + 1]) ++gi;
-        const int64_t s = sg.s[gi];
+        const int32_t s = sg.s[gi];
         const int64_t w = live ? (first[gi] + (f - pre[gi])) * s : w0;
         const int64_t g = sg.g[gi], Lg = g * 32;
         // every L of the group compares word w with words w+g, w+g+1: three words
         // per plane from the tile, once per sample
         uint32_t a[B], lo[B], hi[B];
-#pragma unroll
-        for (int p = 0; p < B; ++p) {
-            a[p] = tl[(w - base) * B + p];
-            lo[p] = tl[(w + g - base) * B + p];
-            hi[p] = tl[(w + g + 1 - base) * B + p];
-        }
+        words.planes(w, a);
+        words.planes(w + g, lo);
+        words.planes(w + g + 1, hi);
         for (int r = 0; r < 32; ++r) {   // uniform
             const int64_t L = Lg + r;
             const bool ok = live && L >= lmin && L <= lmax;
-            uint32_t M = 0u;
-            if (ok) {
-                uint32_t x = 0;
-#pragma unroll
-                for (int p = 0; p < B; ++p) x |= a[p] ^ __builtin_amdgcn_alignbit(hi[p], lo[p], (uint32_t)r);
-                M = ~x;
-                const int64_t lim = n - L - w * 32;
-                if (lim <= 0) M = 0u;
-                else if (lim < 32) M &= (1u << lim) - 1u;
-            }
-            // owner test: the first non-full word among w-1 .. w-s gives the
-            // run's start (all full: the previous sample owns the run)
-            int64_t start = -1;
-            if (__any(M == FULL) && M == FULL) {
-                for (int64_t k0 = 1; k0 <= s && start < 0; k0 += 8) {
-                    uint32_t Mq[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) Mq[i] = k0 + i <= s ? eqL(w - (k0 + i), L) : FULL;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i)
-                        if (start < 0 && Mq[i] != FULL) start = (w - (k0 + i) + 1) * 32 - (int64_t)__clz(~Mq[i]);
-                }
-            }
-            uint64_t own = __ballot(start >= 0);   // uniform
-            while (own) {
-                const int src = __ffsll((unsigned long long)own) - 1;
-                own &= own - 1;
-                const int64_t ws = ((int64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)w, src)) |
-                                   ((int64_t)__builtin_amdgcn_readlane((int)(w >> 32), src) << 32);
-                const int64_t st = ((int64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)start, src)) |
-                                   ((int64_t)__builtin_amdgcn_readlane((int)(start >> 32), src) << 32);
-                const int64_t Lo = ((int64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)L, src));
-                const int64_t Ko = (mc - 1) * Lo;
-                // end: the first non-full word after ws -- one 64-word step here
-                // (global: it may leave the tile), a longer streak is ended by k_streak_end
-                const int64_t q0 = ws + 1;
-                const uint32_t Mq = eq32<B>(P, q0 + lane, Lo, n);   // 0 past the text: ends the scan
-                const uint64_t nb = __ballot(Mq != FULL);
-                if (!nb) {
-                    if (lane == 0) push_pending(out, Lo, st, q0 + 64);
-                    continue;
-                }
-                const int fb = __ffsll((unsigned long long)nb) - 1;
-                const uint32_t Mf = (uint32_t)__builtin_amdgcn_readlane((int)Mq, fb);
-                const int64_t end = (q0 + fb) * 32 + (int64_t)__ffs(~Mf) - 1;
-                if (end - st >= Ko && lane == 0) {
-                    const unsigned long long at = atomicAdd(out.count + seg, 1ull);
-                    put(out, seg, at, Lo, st, end);
-                }
-            }
+            const uint32_t M = ok ? window_mask<B>(a, lo, hi, (uint32_t)r, n - L - w * 32) : 0u;
+            sampled_runs<B>(words, P, n, mc, w, s, L, M, seg, out);
         }
     }
 }
@@ -967,22 +953,15 @@ __global__ __launch_bounds__(256) void k_streak_end(const uint32_t *__restrict__
         for (int64_t q0 = out.pend[3 * e + 2]; end < 0; q0 += 64 * kWide) {
             uint32_t Mq[kWide];
 #pragma unroll
-            for (int i = 0; i < kWide; ++i) Mq[i] = eq32<B>(P, q0 + 64 * i + lane, L, n);   // 0 past the text
+            for (int i = 0; i < kWide; ++i) Mq[i] = eq32<B>(P, 0, q0 + 64 * i + lane, L, n);   // 0 past the text
 #pragma unroll
-            for (int i = 0; i < kWide; ++i) {
-                const uint64_t nb = __ballot(Mq[i] != FULL);
-                if (end < 0 && nb) {
-                    const int f = __ffsll((unsigned long long)nb) - 1;
-                    const uint32_t Mf = (uint32_t)__builtin_amdgcn_readlane((int)Mq[i], f);
-                    end = (q0 + 64 * i + f) * 32 + (int64_t)__ffs(~Mf) - 1;
-                }
+            for (int i = 0; i < kWide; ++i) {   // every step unconditional: behind a branch its loads would sink to it
+                const int64_t e8 = streak_end_step(Mq[i], q0 + 64 * i);
+                if (end < 0) end = e8;   // uniform
             }
         }
-        if (end - st >= (mc - 1) * L && lane == 0) {
-            const int seg = (int)(e & (kCandSegs - 1));
-            const unsigned long long at = atomicAdd(out.count + seg, 1ull);
-            put(out, seg, at, L, st, end);
-        }
+        const int seg = (int)(e & (kCandSegs - 1));
+        if (end - st >= (mc - 1) * L && lane == 0) put(out, seg, atomicAdd(out.count + seg, 1ull), L, st, end);
     }
 }
 
@@ -1010,7 +989,9 @@ void launch_runs(Ctx &c, const uint32_t *P, int64_t n, int32_t lmin, int32_t lma
     }
     for (int64_t g0 = gs; g0 <= (lmax >> 5); g0 += kSparseMax) {
         SparseGroups sg{};
-        sg.ng = 0;
+        // the tile's halo: the largest stride before it (owner tests), the
+        // largest group + 2 words after it (words w + g and w + g + 1 of its last sample)
+        int32_t halo = 0, after = 0;
         for (int64_t g = g0; g <= (lmax >> 5) && sg.ng < kSparseMax; ++g) {
             const int64_t s = sparse_stride(g, lmin, mc);
             sg.g[sg.ng] = (int32_t)g;
@@ -1018,20 +999,15 @@ void launch_runs(Ctx &c, const uint32_t *P, int64_t n, int32_t lmin, int32_t lma
             const int64_t samples = (nwords32 + s - 1) / s;
             sg.woff[sg.ng + 1] = sg.woff[sg.ng] + (samples + 63) / 64;
             ++sg.ng;
+            halo = std::max(halo, (int32_t)s);
+            after = std::max(after, (int32_t)g + 2);
         }
         const int64_t waves = sg.woff[sg.ng];
         if (waves == 0) continue;
-        // the tile's halo: the largest stride before it (owner tests), the
-        // largest group + 2 words after it (words w + g and w + g + 1 of its last sample)
-        int32_t halo = 0, after = 0;
-        for (int gi = 0; gi < sg.ng; ++gi) {
-            halo = std::max(halo, sg.s[gi]);
-            after = std::max(after, sg.g[gi] + 2);
-        }
-        const bool untiled = knob(KN_RUNS_UNTILED) != 0;
         constexpr int T = run_tile<B>();
         const size_t lds = (size_t)(halo + T + after) * B * 4;
-        if (!untiled && halo <= 256 && lds <= 64 * 1024) {   // LDS tiles (BWTMI_RUNS_UNTILED=1: the scattered-sample kernel)
+        // LDS tiles when the halo and the tile fit (BWTMI_RUNS_UNTILED=1: never), else the scattered-sample kernel
+        if (!knob(KN_RUNS_UNTILED) && halo <= 256 && lds <= 64 * 1024) {
             KLAUNCH("k_runs_sparse", 0.0, (k_runs_tiled<B>),
                     dim3((unsigned)((nwords32 + T - 1) / T), (unsigned)std::min(kRunGroupSplit, sg.ng)), dim3(256), lds,
                     c.stream, P, n, nwords32, lmin, lmax, mc, sg, halo, after, out);
@@ -1042,6 +1018,241 @@ void launch_runs(Ctx &c, const uint32_t *P, int64_t n, int32_t lmin, int32_t lma
     }
     KLAUNCH("k_streak_end", 0.0, (k_streak_end<B>), dim3(512), dim3(256), 0, c.stream, P, n, mc, out);
 }
+
+// ------------------------------------------------------------ the driver
+// The scan's small device words (S_MISC3).  The host reads them through the pinned mailbox
+// (kMbWords 8-byte words), one wait per step: the alphabet's presence bits in words 0..3; then
+// count[] in words 0..255 and npend in word kMbNpend; at last two uint32 in word 0 (the final
+// candidate's scan and flag: the hit count) and maxlen in word kMbMaxlen.
+struct ScanWords {
+    unsigned long long count[kCandSegs];   // candidates per segment (reset per attempt)
+    int64_t off[kCandSegs];                // the segments' offsets in the gathered arrays
+    int64_t nlong;                         // candidates with unit length > kThreadPeriodL (k_count_long)
+    unsigned long long npend;              // deferred streak ends pushed (reset per attempt)
+    unsigned long long maxlen;             // the hits' longest span (k_compact)
+};
+constexpr int kMbNpend = kCandSegs, kMbMaxlen = 1, kMbWords = kCandSegs + 8;
+
+// the runtime plane count as a template argument: f(std::integral_constant<int, B>{})
+template <class F>
+void with_planes(int B, F &&f) {
+    if (B == 1) f(std::integral_constant<int, 1>{});
+    else if (B == 2) f(std::integral_constant<int, 2>{});
+    else if (B == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+
+// prim_len / copies of hits [0, nh) of S_HITS
+void period_hits(Ctx &c, const uint8_t *d_text, int64_t nh) {
+    if (nh > 0)
+        KLAUNCH("k_period", 0.0, k_period, dim3(blocks(nh)), dim3(256), 0, c.stream, d_text,
+                c.slot[S_HITS].as<bwtmi_hit>(), nh);
+    HIPCHECK(hipGetLastError());
+}
+// hits [0, nh) of S_HITS into `out`, waited for
+void download_hits(Ctx &c, int64_t nh, HitVec &out) {
+    out.resize((size_t)nh);
+    if (nh > 0)
+        HIPCHECK(hipMemcpyAsync(out.data(), c.slot[S_HITS].p, (size_t)nh * sizeof(bwtmi_hit), hipMemcpyDeviceToHost,
+                                c.stream));
+    scan_wait(c.stream);
+}
+
+// One strict_scan_device call: what its stages share, and the stages in the
+// order they run.  Each stage says what it leaves where.
+struct StrictScan {
+    Ctx &c;
+    hipStream_t st;
+    const uint8_t *d_text;
+    int64_t n;
+    int32_t lmin, lmax, min_copies;
+    bool screen, drop;   // hits go through the nested screen (which may drop those below min_copies)
+    ScanResult &res;
+    ScanWords *sw = nullptr;            // device
+    unsigned long long *mb = nullptr;   // the mailbox
+
+    // min_copies == 1, the whole scan: one lane per unit length (k_mc1), the rows joined in S_HITS
+    void min_copies_one() {
+        const int64_t nL = lmax - lmin + 1;
+        std::vector<int64_t> off((size_t)nL + 1, 0);
+        for (int64_t row = 0; row < nL; ++row) off[(size_t)row + 1] = off[(size_t)row] + n / (lmax - row) + 1;
+        c.slot[S_MISC0].ensure((size_t)(nL + 1) * sizeof(int64_t));
+        c.slot[S_MISC1].ensure((size_t)off[(size_t)nL] * sizeof(bwtmi_hit));
+        c.slot[S_MISC2].ensure((size_t)nL * sizeof(int64_t));
+        HIPCHECK(hipMemcpyAsync(c.slot[S_MISC0].p, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
+        KLAUNCH("k_mc1", 0.0, k_mc1, dim3((unsigned)((nL + 63) / 64)), dim3(64), 0, st, d_text, n, lmin, lmax,
+                c.slot[S_MISC0].as<int64_t>(), c.slot[S_MISC1].as<bwtmi_hit>(), c.slot[S_MISC2].as<int64_t>());
+        HIPCHECK(hipGetLastError());
+        std::vector<int64_t> np((size_t)nL);
+        HIPCHECK(hipMemcpyAsync(np.data(), c.slot[S_MISC2].p, np.size() * 8, hipMemcpyDeviceToHost, st));
+        scan_wait(st);
+        const int64_t nh = std::accumulate(np.begin(), np.end(), int64_t{0});
+        c.slot[S_HITS].ensure((size_t)std::max<int64_t>(nh, 1) * sizeof(bwtmi_hit));
+        int64_t w = 0;
+        for (int64_t row = 0; row < nL; ++row) {   // rows are already in (L desc, start asc) order
+            if (np[(size_t)row])
+                HIPCHECK(hipMemcpyAsync(c.slot[S_HITS].as<bwtmi_hit>() + w,
+                                        c.slot[S_MISC1].as<bwtmi_hit>() + off[(size_t)row],
+                                        (size_t)np[(size_t)row] * sizeof(bwtmi_hit), hipMemcpyDeviceToDevice, st));
+            w += np[(size_t)row];
+        }
+        res.raw = nh;
+        period_hits(c, d_text, nh);
+        if (!screen) return download_hits(c, nh, res.hits);
+        screen_hits_device(c, c.slot[S_HITS].as<bwtmi_hit>(), nh, n, lmax, res.shits, -1, min_copies, drop);
+        c.kresolve();
+    }
+
+    // 1. alphabet -> code width -> the planes P (S_PACK; B per word, 8 zero words past the
+    // text); candidate keys will hold starts < n in their low sb bits
+    struct Packed { int B; uint32_t *P; int sb; };
+    Packed pack() {
+        c.slot[S_COUNTS].ensure(256 * sizeof(unsigned long long));
+        HIPCHECK(hipMemsetAsync(c.slot[S_COUNTS].p, 0, 256 * sizeof(unsigned long long), st));
+        KLAUNCH("k_present", (double)n, k_present, dim3(1024), dim3(256), 0, st, d_text, n,
+                c.slot[S_COUNTS].as<unsigned long long>());
+        HIPCHECK(hipMemcpyAsync(mb, c.slot[S_COUNTS].p, 32, hipMemcpyDeviceToHost, st));   // 256 presence bits
+        scan_wait(st);
+        uint8_t code[256] = {0};
+        int sigma = 0;
+        for (int b = 0; b < 256; ++b)
+            if ((mb[b >> 6] >> (b & 63)) & 1ull) code[b] = (uint8_t)sigma++;
+        const int B = sigma <= 2 ? 1 : (sigma <= 4 ? 2 : (sigma <= 16 ? 4 : 8));
+        const int64_t nwords = (n + 31) / 32 + 8;   // + padding read by the window of the last words
+        int sb = 1;
+        while (sb < 63 && (1ll << sb) < n) ++sb;
+        c.slot[S_PACK].ensure((size_t)nwords * B * sizeof(uint32_t) + 256);
+        uint8_t *d_code = c.slot[S_PACK].as<uint8_t>() + nwords * B * sizeof(uint32_t);
+        HIPCHECK(hipMemcpyAsync(d_code, code, 256, hipMemcpyHostToDevice, st));
+        uint32_t *P = c.slot[S_PACK].as<uint32_t>();
+        HIPCHECK(hipMemsetAsync(P, 0, (size_t)nwords * B * sizeof(uint32_t), st));
+        with_planes(B, [&](auto b) {
+            KLAUNCH("k_pack", 0.0, k_pack<decltype(b)::value>, dim3(blocks(nwords)), dim3(256), 0, st, d_text, n,
+                    d_code, P, nwords - 8);
+        });
+        HIPCHECK(hipGetLastError());
+        return {B, P, sb};
+    }
+
+    // 2. candidate runs into segments (again with larger ones when they or the list of
+    // deferred streaks overflow), gathered into S_CAND_K / S_CAND_V; returns their number
+    int64_t candidates(const Packed &pk) {
+        int64_t seg_cap = std::max<int64_t>(1 << 12, n / 8 / kCandSegs + 1024), pend_cap = 1 << 16;
+        const unsigned long long *segn = mb;   // [kCandSegs], as the last attempt left them
+        unsigned long long ncand = 0, mx = 0;
+        for (int attempt = 0;; ++attempt) {
+            c.slot[S_CAND_K2].ensure((size_t)(seg_cap * kCandSegs) * sizeof(uint64_t));
+            c.slot[S_CAND_V2].ensure((size_t)(seg_cap * kCandSegs) * sizeof(uint64_t));
+            c.slot[S_MISC2].ensure((size_t)pend_cap * 3 * sizeof(int64_t));
+            HIPCHECK(hipMemsetAsync(sw->count, 0, sizeof sw->count, st));
+            HIPCHECK(hipMemsetAsync(&sw->npend, 0, sizeof sw->npend, st));
+            CandOut co{c.slot[S_CAND_K2].as<uint64_t>(), c.slot[S_CAND_V2].as<uint64_t>(), sw->count, seg_cap, lmax,
+                       pk.sb, c.slot[S_MISC2].as<int64_t>(), &sw->npend, pend_cap};
+            hipEvent_t ka = nullptr, kb = nullptr;
+            if (c.timing) {
+                HIPCHECK(hipEventCreate(&ka));
+                HIPCHECK(hipEventCreate(&kb));
+                HIPCHECK(hipEventRecord(ka, st));
+            }
+            with_planes(pk.B, [&](auto b) { launch_runs<decltype(b)::value>(c, pk.P, n, lmin, lmax, min_copies, co); });
+            HIPCHECK(hipGetLastError());
+            if (c.timing) HIPCHECK(hipEventRecord(kb, st));
+            HIPCHECK(hipMemcpyAsync(mb, sw->count, sizeof sw->count, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipMemcpyAsync(mb + kMbNpend, &sw->npend, 8, hipMemcpyDeviceToHost, st));
+            scan_wait(st);
+            const unsigned long long npend = mb[kMbNpend];
+            if (c.timing) {
+                float ms = 0;
+                HIPCHECK(hipEventElapsedTime(&ms, ka, kb));
+                c.last_dom_ms = res.kernel_ms = ms;
+                c.last_dom_launches = 1;
+                c.dom_name = "k_runs";
+                (void)hipEventDestroy(ka), (void)hipEventDestroy(kb);
+            }
+            ncand = std::accumulate(segn, segn + kCandSegs, 0ull);
+            mx = *std::max_element(segn, segn + kCandSegs);
+            if ((int64_t)mx <= seg_cap && (int64_t)npend <= pend_cap) break;
+            if (attempt >= 2)
+                fail(BWTMI_E_STATE, "strict scan: candidate segments overflow after %d attempts", attempt + 1);
+            // the counts are exact, so the next attempt fits (but streaks lost from the list
+            // were not counted as candidates: it may find more)
+            if ((int64_t)mx > seg_cap) seg_cap = (int64_t)mx + (int64_t)mx / 4 + 1024;
+            if ((int64_t)npend > pend_cap) pend_cap = (int64_t)npend + (int64_t)npend / 4 + 1024;
+            else if ((int64_t)npend > pend_cap / 2) pend_cap *= 2;
+        }
+        if (ncand == 0) return 0;
+        int64_t off[kCandSegs];   // in segment order (any order would do: a radix sort follows)
+        for (int q = 0; q < kCandSegs; ++q) off[q] = q ? off[q - 1] + (int64_t)segn[q - 1] : 0;
+        c.slot[S_CAND_K].ensure((size_t)ncand * sizeof(uint64_t));
+        c.slot[S_CAND_V].ensure((size_t)ncand * sizeof(uint64_t));
+        HIPCHECK(hipMemcpyAsync(sw->off, off, sizeof off, hipMemcpyHostToDevice, st));
+        KLAUNCH("k_cand_gather", 0.0, k_cand_gather, dim3((unsigned)((mx + 255) / 256), kCandSegs), dim3(256), 0, st,
+                c.slot[S_CAND_K2].as<uint64_t>(), c.slot[S_CAND_V2].as<uint64_t>(), sw->count, sw->off, seg_cap,
+                c.slot[S_CAND_K].as<uint64_t>(), c.slot[S_CAND_V].as<uint64_t>());
+        HIPCHECK(hipGetLastError());
+        return (int64_t)ncand;
+    }
+
+    // 3. the candidates in the reference's order (L desc, start asc); 4. carry resolution,
+    // compaction into S_HITS and the periods.  Hits are a subset of the candidates, so all of it
+    // runs before the host learns the hit count, which it reads with the longest span in one wait.
+    struct Hits { int64_t nh, maxlen; };   // hits in S_HITS; their longest span (the screen's key width)
+    Hits resolve(int sb, int64_t nc) {
+        uint64_t *keys = c.slot[S_CAND_K].as<uint64_t>(), *vals = c.slot[S_CAND_V].as<uint64_t>();
+        int hb = 0;
+        while ((1ll << hb) <= (int64_t)lmax) ++hb;
+        radix_sort_pairs(c, keys, vals, nc, 0, ((sb + hb + 7) / 8) * 8);
+        c.slot[S_MISC0].ensure((size_t)nc * sizeof(int64_t));
+        c.slot[S_MISC1].ensure((size_t)nc * sizeof(int64_t));
+        c.slot[S_FLAG].ensure((size_t)nc * sizeof(uint32_t));
+        c.slot[S_SCAN].ensure((size_t)(nc + 1) * sizeof(uint32_t));
+        c.slot[S_HITS].ensure((size_t)nc * sizeof(bwtmi_hit));
+        int64_t *hit_i = c.slot[S_MISC0].as<int64_t>(), *hit_c = c.slot[S_MISC1].as<int64_t>();
+        uint32_t *flag = c.slot[S_FLAG].as<uint32_t>(), *pos = c.slot[S_SCAN].as<uint32_t>();
+        bwtmi_hit *hits = c.slot[S_HITS].as<bwtmi_hit>();
+        KLAUNCH("k_resolve", 0.0, k_resolve, dim3(blocks(nc)), dim3(256), 0, st, keys, vals, nc, lmax, sb,
+                (int64_t)min_copies, hit_i, hit_c, flag);
+        HIPCHECK(hipMemsetAsync(pos + nc, 0, sizeof(uint32_t), st));
+        exclusive_scan<uint32_t>(c, flag, pos, nc);
+        KLAUNCH("k_count_long", 0.0, k_count_long, dim3(1), dim3(64), 0, st, keys, nc, lmax, sb, kThreadPeriodL,
+                &sw->nlong);
+        HIPCHECK(hipMemsetAsync(&sw->maxlen, 0, sizeof sw->maxlen, st));
+        KLAUNCH("k_compact", 0.0, k_compact, dim3(blocks(nc)), dim3(256), 0, st, keys, nc, lmax, sb, hit_i, hit_c, flag,
+                pos, d_text, hits, &sw->maxlen);
+        KLAUNCH("k_period_wave", 0.0, k_period_wave, dim3((unsigned)std::min<int64_t>(2048, (nc * 64 + 255) / 256)),
+                dim3(256), 0, st, keys, &sw->nlong, lmax, sb, hit_i, hit_c, flag, pos, d_text, hits);
+        HIPCHECK(hipGetLastError());
+        uint32_t *mb32 = reinterpret_cast<uint32_t *>(mb);
+        HIPCHECK(hipMemcpyAsync(mb32, pos + nc - 1, 4, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(mb32 + 1, flag + nc - 1, 4, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(mb + kMbMaxlen, &sw->maxlen, 8, hipMemcpyDeviceToHost, st));
+        scan_wait(st);
+        c.checks_verify("the strict scan's hit count");
+        return {(int64_t)mb32[0] + mb32[1], (int64_t)mb[kMbMaxlen]};
+    }
+
+    // 5. the hits of S_HITS through the nested screen, or downloaded as they are
+    void deliver(const Hits &h) {
+        if (screen) {
+            // records c.ev1 behind its kernels; its hits download may still be landing
+            // (res.shits.wait), every kernel has finished
+            screen_hits_device(c, c.slot[S_HITS].as<bwtmi_hit>(), h.nh, n, lmax, res.shits, h.maxlen, min_copies,
+                               drop);
+            if (c.timing && !res.shits.landing) HIPCHECK(hipEventRecord(c.ev1, st));
+            if (!res.shits.landing) scan_wait(st);
+            else if (c.timing) while (hipEventQuery(c.ev1) == hipErrorNotReady) __builtin_ia32_pause();
+        } else {
+            if (c.timing) HIPCHECK(hipEventRecord(c.ev1, st));
+            download_hits(c, h.nh, res.hits);
+        }
+        c.kresolve();
+        if (c.timing) {
+            float ms = 0;
+            HIPCHECK(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+            c.last_total_ms = ms;
+        }
+    }
+};
 
 }  // namespace
 
@@ -1100,11 +1311,8 @@ void strict_scan_mm_device(Ctx &c, const uint8_t *d_text, int64_t n, int32_t min
     if (!nh) return;
     c.slot[S_HITS].ensure((size_t)nh * sizeof(bwtmi_hit));
     HIPCHECK(hipMemcpyAsync(c.slot[S_HITS].p, hits.data(), (size_t)nh * sizeof(bwtmi_hit), hipMemcpyHostToDevice, st));
-    KLAUNCH("k_period", 0.0, k_period, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, st, d_text,
-            c.slot[S_HITS].as<bwtmi_hit>(), nh);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(hits.data(), c.slot[S_HITS].p, (size_t)nh * sizeof(bwtmi_hit), hipMemcpyDeviceToHost, st));
-    scan_wait(st);
+    period_hits(c, d_text, nh);
+    download_hits(c, nh, hits);
 }
 
 void strict_scan_device(Ctx &c, const uint8_t *d_text, int64_t n, int32_t min_unit, int32_t max_unit,
@@ -1116,230 +1324,21 @@ void strict_scan_device(Ctx &c, const uint8_t *d_text, int64_t n, int32_t min_un
     res.raw = 0;
     res.screened = screen;
     if (min_copies <= 0) fail(BWTMI_E_ARG, "min_copies must be positive");
-    // bwt.py:1920-1921
-    const int64_t maxL = std::min<int64_t>(max_unit, n / min_copies);
+    const int64_t maxL = std::min<int64_t>(max_unit, n / min_copies);   // bwt.py:1920-1921
     if (n <= 0 || maxL < min_unit || maxL < 1) return;
-    const int32_t lmin = std::max<int32_t>(1, min_unit), lmax = (int32_t)maxL;
-    hipStream_t st = c.stream;
-    if (c.timing) HIPCHECK(hipEventRecord(c.ev0, st));
-
-    if (min_copies == 1) {   // degenerate but reachable from --min-copies 1
-        const int64_t nL = lmax - lmin + 1;
-        std::vector<int64_t> off((size_t)nL + 1, 0);
-        for (int64_t row = 0; row < nL; ++row) off[(size_t)row + 1] = off[(size_t)row] + n / (lmax - row) + 1;
-        const int64_t tot = off[(size_t)nL];
-        c.slot[S_MISC0].ensure((size_t)(nL + 1) * sizeof(int64_t));
-        c.slot[S_MISC1].ensure((size_t)tot * sizeof(bwtmi_hit));
-        c.slot[S_MISC2].ensure((size_t)nL * sizeof(int64_t));
-        HIPCHECK(hipMemcpyAsync(c.slot[S_MISC0].p, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
-        KLAUNCH("k_mc1", 0.0, k_mc1, dim3((unsigned)((nL + 63) / 64)), dim3(64), 0, st, d_text, n, lmin, lmax,
-                           c.slot[S_MISC0].as<int64_t>(), c.slot[S_MISC1].as<bwtmi_hit>(),
-                           c.slot[S_MISC2].as<int64_t>());
-        HIPCHECK(hipGetLastError());
-        std::vector<int64_t> np((size_t)nL);
-        HIPCHECK(hipMemcpyAsync(np.data(), c.slot[S_MISC2].p, np.size() * 8, hipMemcpyDeviceToHost, st));
-        scan_wait(st);
-        int64_t nh = 0;
-        for (auto v : np) nh += v;
-        c.slot[S_HITS].ensure((size_t)std::max<int64_t>(nh, 1) * sizeof(bwtmi_hit));
-        int64_t w = 0;
-        for (int64_t row = 0; row < nL; ++row) {   // rows are already in (L desc, start asc) order
-            if (np[(size_t)row])
-                HIPCHECK(hipMemcpyAsync(c.slot[S_HITS].as<bwtmi_hit>() + w,
-                                        c.slot[S_MISC1].as<bwtmi_hit>() + off[(size_t)row],
-                                        (size_t)np[(size_t)row] * sizeof(bwtmi_hit), hipMemcpyDeviceToDevice, st));
-            w += np[(size_t)row];
-        }
-        if (nh > 0)
-            KLAUNCH("k_period", 0.0, k_period, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, st, d_text,
-                               c.slot[S_HITS].as<bwtmi_hit>(), nh);
-        HIPCHECK(hipGetLastError());
-        res.raw = nh;
-        if (screen) {
-            screen_hits_device(c, c.slot[S_HITS].as<bwtmi_hit>(), nh, n, lmax, res.shits, -1, min_copies, drop_min_copies > 0);
-            c.kresolve();
-            return;
-        }
-        res.hits.resize((size_t)nh);
-        if (nh > 0)
-            HIPCHECK(hipMemcpyAsync(res.hits.data(), c.slot[S_HITS].p, (size_t)nh * sizeof(bwtmi_hit),
-                                    hipMemcpyDeviceToHost, st));
-        scan_wait(st);
-        return;
-    }
-
-    // 1. alphabet -> code width
-    c.slot[S_COUNTS].ensure(256 * sizeof(unsigned long long));
-    HIPCHECK(hipMemsetAsync(c.slot[S_COUNTS].p, 0, 256 * sizeof(unsigned long long), st));
-    KLAUNCH("k_present", (double)n, k_present, dim3(1024), dim3(256), 0, st, d_text, n,
-            c.slot[S_COUNTS].as<unsigned long long>());
-    // the small host reads below go through the pinned mailbox, one wait per step
-    unsigned long long *mb = c.mailbox<unsigned long long>(kCandSegs + 8);
-    unsigned long long present[4];
-    HIPCHECK(hipMemcpyAsync(mb, c.slot[S_COUNTS].p, sizeof present, hipMemcpyDeviceToHost, st));
-    scan_wait(st);
-    std::memcpy(present, mb, sizeof present);
-    uint8_t code[256] = {0};
-    int sigma = 0;
-    for (int b = 0; b < 256; ++b)
-        if ((present[b >> 6] >> (b & 63)) & 1ull) code[b] = (uint8_t)sigma++;
-    const int B = sigma <= 2 ? 1 : (sigma <= 4 ? 2 : (sigma <= 16 ? 4 : 8));
-    const int64_t nwords = (n + 31) / 32 + 8;   // + padding read by the window of the last words
-    int sb = 1;   // candidate keys hold starts < n in their low sb bits
-    while (sb < 63 && (1ll << sb) < n) ++sb;
-    c.slot[S_PACK].ensure((size_t)nwords * B * sizeof(uint32_t) + 256);
-    uint8_t *d_code = c.slot[S_PACK].as<uint8_t>() + nwords * B * sizeof(uint32_t);
-    HIPCHECK(hipMemcpyAsync(d_code, code, 256, hipMemcpyHostToDevice, st));
-    uint32_t *P = c.slot[S_PACK].as<uint32_t>();
-    HIPCHECK(hipMemsetAsync(P, 0, (size_t)nwords * B * sizeof(uint32_t), st));
-    const unsigned pgrid = (unsigned)((nwords + 255) / 256);
-    if (B == 1) KLAUNCH("k_pack", 0.0, k_pack<1>, dim3(pgrid), dim3(256), 0, st, d_text, n, d_code, P, nwords - 8);
-    else if (B == 2) KLAUNCH("k_pack", 0.0, k_pack<2>, dim3(pgrid), dim3(256), 0, st, d_text, n, d_code, P, nwords - 8);
-    else if (B == 4) KLAUNCH("k_pack", 0.0, k_pack<4>, dim3(pgrid), dim3(256), 0, st, d_text, n, d_code, P, nwords - 8);
-    else KLAUNCH("k_pack", 0.0, k_pack<8>, dim3(pgrid), dim3(256), 0, st, d_text, n, d_code, P, nwords - 8);
-    HIPCHECK(hipGetLastError());
-
-    // 2. candidate runs (segmented output, compacted below)
-    int64_t seg_cap = std::max<int64_t>(1 << 12, n / 8 / kCandSegs + 1024);
-    unsigned long long segn[kCandSegs] = {0};
-    unsigned long long ncand = 0;
-    c.slot[S_MISC3].ensure(kCandSegs * (sizeof(unsigned long long) + sizeof(int64_t)) + 64);
-    unsigned long long *d_count = c.slot[S_MISC3].as<unsigned long long>();
-    int64_t *d_off = reinterpret_cast<int64_t *>(d_count + kCandSegs);
-    // deferred streak ends: the counter sits after the segment counts (both reset per attempt)
-    unsigned long long *d_npend = reinterpret_cast<unsigned long long *>(d_count + kCandSegs + kCandSegs + 2);
-    int64_t pend_cap = 1 << 16;
-    for (int attempt = 0;; ++attempt) {
-        c.slot[S_CAND_K2].ensure((size_t)(seg_cap * kCandSegs) * sizeof(uint64_t));
-        c.slot[S_CAND_V2].ensure((size_t)(seg_cap * kCandSegs) * sizeof(uint64_t));
-        c.slot[S_MISC2].ensure((size_t)pend_cap * 3 * sizeof(int64_t));
-        HIPCHECK(hipMemsetAsync(d_count, 0, kCandSegs * sizeof(unsigned long long), st));
-        HIPCHECK(hipMemsetAsync(d_npend, 0, sizeof(unsigned long long), st));
-        CandOut co{c.slot[S_CAND_K2].as<uint64_t>(), c.slot[S_CAND_V2].as<uint64_t>(), d_count, seg_cap, lmax, sb,
-                   c.slot[S_MISC2].as<int64_t>(), d_npend, pend_cap};
-        hipEvent_t ka = nullptr, kb = nullptr;
-        if (c.timing) {
-            HIPCHECK(hipEventCreate(&ka));
-            HIPCHECK(hipEventCreate(&kb));
-            HIPCHECK(hipEventRecord(ka, st));
-        }
-        if (B == 1) launch_runs<1>(c, P, n, lmin, lmax, min_copies, co);
-        else if (B == 2) launch_runs<2>(c, P, n, lmin, lmax, min_copies, co);
-        else if (B == 4) launch_runs<4>(c, P, n, lmin, lmax, min_copies, co);
-        else launch_runs<8>(c, P, n, lmin, lmax, min_copies, co);
-        HIPCHECK(hipGetLastError());
-        if (c.timing) HIPCHECK(hipEventRecord(kb, st));
-        HIPCHECK(hipMemcpyAsync(mb, d_count, sizeof segn, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipMemcpyAsync(mb + kCandSegs, d_npend, 8, hipMemcpyDeviceToHost, st));
-        scan_wait(st);
-        std::memcpy(segn, mb, sizeof segn);
-        const unsigned long long npend = mb[kCandSegs];
-        if (c.timing) {
-            float ms = 0;
-            HIPCHECK(hipEventElapsedTime(&ms, ka, kb));
-            c.last_dom_ms = ms;
-            c.last_dom_launches = 1;
-            c.dom_name = "k_runs";
-            res.kernel_ms = ms;
-            (void)hipEventDestroy(ka);
-            (void)hipEventDestroy(kb);
-        }
-        unsigned long long mx = 0;
-        ncand = 0;
-        for (int q = 0; q < kCandSegs; ++q) {
-            ncand += segn[q];
-            mx = std::max(mx, segn[q]);
-        }
-        if ((int64_t)mx <= seg_cap && (int64_t)npend <= pend_cap) break;
-        if (attempt >= 2) fail(BWTMI_E_STATE, "strict scan: candidate segments overflow after %d attempts", attempt + 1);
-        if ((int64_t)mx > seg_cap) seg_cap = (int64_t)mx + (int64_t)mx / 4 + 1024;   // exact counts: the next attempt fits
-        // (lost streaks were not counted as candidates: the next attempt may find more)
-        if ((int64_t)npend > pend_cap) pend_cap = (int64_t)npend + (int64_t)npend / 4 + 1024;
-        else if ((int64_t)npend > pend_cap / 2) pend_cap *= 2;
-    }
-    if (ncand > 0) {
-        int64_t off[kCandSegs];
-        unsigned long long mx = 0;
-        for (int q = 0; q < kCandSegs; ++q) {
-            off[q] = q ? off[q - 1] + (int64_t)segn[q - 1] : 0;
-            mx = std::max(mx, segn[q]);
-        }
-        c.slot[S_CAND_K].ensure((size_t)ncand * sizeof(uint64_t));
-        c.slot[S_CAND_V].ensure((size_t)ncand * sizeof(uint64_t));
-        HIPCHECK(hipMemcpyAsync(d_off, off, sizeof off, hipMemcpyHostToDevice, st));
-        KLAUNCH("k_cand_gather", 0.0, k_cand_gather, dim3((unsigned)((mx + 255) / 256), kCandSegs), dim3(256), 0, st,
-                           c.slot[S_CAND_K2].as<uint64_t>(), c.slot[S_CAND_V2].as<uint64_t>(), d_count, d_off,
-                           seg_cap, c.slot[S_CAND_K].as<uint64_t>(), c.slot[S_CAND_V].as<uint64_t>());
-        HIPCHECK(hipGetLastError());
-    }
-    const int64_t nc = (int64_t)ncand;
-    res.candidates = nc;
+    StrictScan s{c, c.stream, d_text, n, std::max<int32_t>(1, min_unit), (int32_t)maxL, min_copies, screen,
+                 drop_min_copies > 0, res};
+    if (c.timing) HIPCHECK(hipEventRecord(c.ev0, s.st));
+    if (min_copies == 1) return s.min_copies_one();   // degenerate but reachable from --min-copies 1
+    c.slot[S_MISC3].ensure(sizeof(ScanWords));
+    s.sw = c.slot[S_MISC3].as<ScanWords>();
+    s.mb = c.mailbox<unsigned long long>(kMbWords);
+    const StrictScan::Packed pk = s.pack();
+    const int64_t nc = res.candidates = s.candidates(pk);
     if (nc == 0) return;
-
-    // 3. order candidates as the reference emits them: L desc, start asc
-    int hb = 0;
-    while ((1ll << hb) <= (int64_t)lmax) ++hb;
-    radix_sort_pairs(c, c.slot[S_CAND_K].as<uint64_t>(), c.slot[S_CAND_V].as<uint64_t>(), nc, 0,
-                     ((sb + hb + 7) / 8) * 8);
-
-    // 4. carry resolution + compaction
-    c.slot[S_MISC0].ensure((size_t)nc * sizeof(int64_t));
-    c.slot[S_MISC1].ensure((size_t)nc * sizeof(int64_t));
-    c.slot[S_FLAG].ensure((size_t)nc * sizeof(uint32_t));
-    c.slot[S_SCAN].ensure((size_t)(nc + 1) * sizeof(uint32_t));
-    const unsigned g = (unsigned)((nc + 255) / 256);
-    KLAUNCH("k_resolve", 0.0, k_resolve, dim3(g), dim3(256), 0, st, c.slot[S_CAND_K].as<uint64_t>(),
-                       c.slot[S_CAND_V].as<uint64_t>(), nc, lmax, sb, (int64_t)min_copies, c.slot[S_MISC0].as<int64_t>(),
-                       c.slot[S_MISC1].as<int64_t>(), c.slot[S_FLAG].as<uint32_t>());
-    HIPCHECK(hipMemsetAsync(c.slot[S_SCAN].as<uint32_t>() + nc, 0, sizeof(uint32_t), st));
-    exclusive_scan<uint32_t>(c, c.slot[S_FLAG].as<uint32_t>(), c.slot[S_SCAN].as<uint32_t>(), nc);
-    int64_t *d_nlong = d_off + kCandSegs;   // after the segment offsets
-    KLAUNCH("k_count_long", 0.0, k_count_long, dim3(1), dim3(64), 0, st, c.slot[S_CAND_K].as<uint64_t>(), nc, lmax,
-            sb, kThreadPeriodL, d_nlong);
-    // hits are a subset of the candidates: the compaction and the long units'
-    // periods run before the host learns the hit count, which it reads with the
-    // longest span in one wait
-    c.slot[S_HITS].ensure((size_t)nc * sizeof(bwtmi_hit));
-    unsigned long long *d_maxlen = d_npend + 1;   // the hits' longest span, reduced by k_compact
-    HIPCHECK(hipMemsetAsync(d_maxlen, 0, 8, st));
-    KLAUNCH("k_compact", 0.0, k_compact, dim3(g), dim3(256), 0, st, c.slot[S_CAND_K].as<uint64_t>(), nc, lmax, sb,
-                       c.slot[S_MISC0].as<int64_t>(), c.slot[S_MISC1].as<int64_t>(), c.slot[S_FLAG].as<uint32_t>(),
-                       c.slot[S_SCAN].as<uint32_t>(), d_text, c.slot[S_HITS].as<bwtmi_hit>(), d_maxlen);
-    KLAUNCH("k_period_wave", 0.0, k_period_wave, dim3((unsigned)std::min<int64_t>(2048, (nc * 64 + 255) / 256)),
-            dim3(256), 0, st, c.slot[S_CAND_K].as<uint64_t>(), d_nlong, lmax, sb, c.slot[S_MISC0].as<int64_t>(),
-            c.slot[S_MISC1].as<int64_t>(), c.slot[S_FLAG].as<uint32_t>(), c.slot[S_SCAN].as<uint32_t>(), d_text,
-            c.slot[S_HITS].as<bwtmi_hit>());
-    HIPCHECK(hipGetLastError());
-    uint32_t *mb32 = reinterpret_cast<uint32_t *>(mb);
-    HIPCHECK(hipMemcpyAsync(mb32, c.slot[S_SCAN].as<uint32_t>() + nc - 1, 4, hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipMemcpyAsync(mb32 + 1, c.slot[S_FLAG].as<uint32_t>() + nc - 1, 4, hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipMemcpyAsync(mb + 1, d_maxlen, 8, hipMemcpyDeviceToHost, st));
-    scan_wait(st);
-    c.checks_verify("the strict scan's hit count");
-    const int64_t nh = (int64_t)mb32[0] + mb32[1];
-    const int64_t maxlen = (int64_t)mb[1];
-    res.raw = nh;
-    if (screen) {
-        // records c.ev1 behind its kernels; its hits download may still be landing
-        // (res.shits.wait), every kernel has finished
-        screen_hits_device(c, c.slot[S_HITS].as<bwtmi_hit>(), nh, n, lmax, res.shits, maxlen, min_copies, drop_min_copies > 0);
-        if (c.timing && !res.shits.landing) HIPCHECK(hipEventRecord(c.ev1, st));
-        if (!res.shits.landing) scan_wait(st);
-        else if (c.timing) while (hipEventQuery(c.ev1) == hipErrorNotReady) __builtin_ia32_pause();
-    } else {
-        if (c.timing) HIPCHECK(hipEventRecord(c.ev1, st));
-        res.hits.resize((size_t)nh);
-        if (nh > 0)
-            HIPCHECK(hipMemcpyAsync(res.hits.data(), c.slot[S_HITS].p, (size_t)nh * sizeof(bwtmi_hit),
-                                    hipMemcpyDeviceToHost, st));
-        scan_wait(st);
-    }
-    c.kresolve();
-    if (c.timing) {
-        float ms = 0;
-        HIPCHECK(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        c.last_total_ms = ms;
-    }
+    const StrictScan::Hits h = s.resolve(pk.sb, nc);
+    res.raw = h.nh;
+    s.deliver(h);
 }
 
 }  // namespace bwtmi

@@ -131,15 +131,36 @@ def test_strict_scan_long_units_tile_halo(gpu_ctx):
     _same(four, 1, 1500, 2)
 
 
-@pytest.mark.parametrize("kv", [{"RUNS_DENSE": 1}, {"RUNS_UNTILED": 1}])
+def test_strict_scan_untiled_by_stride(gpu_ctx):
+    """The sampled groups leave the LDS tiles for the global planes when a
+    launch's largest stride exceeds 256 words.  min_copies 10 and max_unit 1000:
+    the last group starts at L = 992, K = 9 * 992, stride (9 * 992 - 31) // 32 =
+    278 > 256, so groups 1-31 (one launch) take the untiled kernel at default
+    knobs.  A 950-base array of 12 copies qualifies for L = 918..950 (strides
+    > 256), a 37-base array of 300 for its multiples, and the A run defers its
+    end to k_streak_end for every L.  Then the same on 4 planes."""
+    t = bytearray(_rng_text(40000, b"ACGT", 5))
+    t[300:300 + 950 * 12] = _rng_text(950, b"ACGT", 6) * 12
+    t[14000:14000 + 37 * 300] = _rng_text(37, b"ACGT", 7) * 300
+    t[30000:39500] = b"A" * 9500
+    assert _same(bytes(t), 1, 1000, 10) > 0
+    assert (_gpu_hits(bytes(t), 1, 1000, 10)[:, 2] >= 918).any()
+    r = np.random.default_rng(8)
+    for k, p in enumerate(r.choice(np.r_[0:300, 11700:14000, 25100:30000, 39500:40000], 20, replace=False)):
+        t[int(p)] = b"NR"[k & 1]
+    assert _same(bytes(t), 1, 1000, 10) > 0
+
+
+@pytest.mark.parametrize("kv", [{"RUNS_DENSE": 1}, {"RUNS_UNTILED": 1}, {}])
 def test_strict_scan_alternate_kernels_vs_oracle(gpu_ctx, kv):
     """The strict scan's alternate paths (BWTMI_RUNS_DENSE: every group in the
-    dense kernel; BWTMI_RUNS_UNTILED: sampled groups straight from the planes)
-    find the same hits: planted arrays on 2- and 4-plane texts, long units
-    across tile ends, homopolymers."""
+    dense kernel; BWTMI_RUNS_UNTILED: sampled groups straight from the planes;
+    default knobs: from LDS tiles) find the same hits: planted arrays on 1-,
+    2-, 4- and 8-plane texts, long units across tile ends, homopolymers."""
     from bwtmi import _lib
     texts = [_planted(120_000, 91), _planted(60_000, 92, b"ACGTNR", max_unit=700),
-             b"A" * 4000 + _rng_text(3000, b"ACGT", 93) + b"CAG" * 900]
+             b"A" * 4000 + _rng_text(3000, b"ACGT", 93) + b"CAG" * 900,
+             _planted(20_000, 95, b"AC", max_unit=300), _planted(20_000, 96, bytes(range(65, 90)), max_unit=300)]
     with _lib.knobs(**kv):
         for seq in texts:
             for mc in (2, 3, 5):
