@@ -33,6 +33,11 @@ class Params(C.Structure):
                 ("build_index", C.c_int32), ("sa_sample", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ChainParams(C.Structure):
+    _fields_ = [("max_gap", C.c_int32), ("bandwidth", C.c_int32), ("max_pred", C.c_int32),
+                ("min_score", C.c_int32), ("min_anchors", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class LibParams(C.Structure):
     _fields_ = [("min_period", C.c_int32), ("max_period", C.c_int32), ("max_short_motif", C.c_int32),
                 ("min_copies", C.c_int32), ("min_array_length", C.c_int32), ("allow_mismatches", C.c_int32),
@@ -83,6 +88,11 @@ _SIGS = {
                                [C.POINTER(C.c_void_p)] * 7 + [C.POINTER(C.c_int64)] * 4),
     "bwtmi_index_smem_long_batch": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_uint32, C.c_int64, C.c_int64] +
                                     [C.POINTER(C.c_void_p)] * 7 + [C.POINTER(C.c_int64)] * 5),
+    "bwtmi_chain_anchors": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.POINTER(ChainParams)] +
+                            [C.POINTER(C.c_void_p)] * 9 + [C.POINTER(C.c_int64)] * 3),
+    "bwtmi_index_map_batch": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_uint32, C.c_int64, C.c_int64,
+                                        C.POINTER(ChainParams)] + [C.POINTER(C.c_void_p)] * 12 +
+                              [C.POINTER(C.c_int64)] * 6),
     "bwtmi_index_lcp_plateaus": (C.c_int, [_P, _P, C.POINTER(LibParams), C.POINTER(C.c_void_p),
                                            C.POINTER(C.c_int64)]),
     "bwtmi_index_short_imperfect": (C.c_int, [_P, _P, C.POINTER(LibParams), _P, C.c_int64, _P, C.c_int32]),
@@ -334,6 +344,68 @@ def screen_hits(h, hits, text_len: int, min_copies: int = 3, drop: bool = False,
         return rows[:n.value * 4].reshape(-1, 4).copy()
     finally:
         lib().bwtmi_free(out)
+
+
+CHAIN_PARAMS = ("max_gap", "bandwidth", "max_pred", "min_score", "min_anchors")
+
+
+def chain_params(**kv) -> ChainParams:
+    """bwtmi_chain_params from keyword arguments (absent or None: the default)."""
+    bad = set(kv) - set(CHAIN_PARAMS) - {"reserved"}
+    if bad:
+        raise TypeError(f"unknown chain parameter(s): {', '.join(sorted(bad))}")
+    p = ChainParams()
+    for k in CHAIN_PARAMS:
+        if kv.get(k) is not None:
+            if int(kv[k]) <= 0:
+                raise ValueError(f"{k} must be positive")
+            setattr(p, k, int(kv[k]))
+    for i, v in enumerate(kv.get("reserved") or ()):
+        p.reserved[i] = int(v)
+    return p
+
+
+def take(p, dtype, count: int):
+    """A copy of `count` elements of `dtype` at the library's malloc'd block p."""
+    import numpy as np
+    if not count:
+        return np.zeros(0, dtype=dtype)
+    return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(count,)).copy()
+
+
+def chain_anchors(h, group_off, q, r, length, **params) -> dict:
+    """The device chainer (bwtmi_chain_anchors) on anchors (q, r, length) in
+    groups group_off[ng + 1]: a dict of chain_off, score, n_anchors, qstart, qend,
+    rstart, rend, member_off, member (input indices) and evals.  ValueError on
+    BWTMI_E_ARG."""
+    import numpy as np
+    go = np.ascontiguousarray(group_off, dtype=np.int64)
+    aq, ar, al = (np.ascontiguousarray(a, dtype=t) for a, t in ((q, np.int32), (r, np.int64), (length, np.int32)))
+    if go.ndim != 1 or go.size < 1 or not aq.size == ar.size == al.size:
+        raise ValueError("group_off needs ng + 1 entries, q / r / length equal sizes")
+    cp = chain_params(**params)
+    ptrs = [C.c_void_p() for _ in range(9)]
+    nc, nm, ev = C.c_int64(-1), C.c_int64(-1), C.c_int64(0)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    rc = lib().bwtmi_chain_anchors(h, go.ctypes.data_as(C.c_void_p), go.size - 1, ptr(aq), ptr(ar), ptr(al), C.byref(cp),
+                                   *[C.byref(p) for p in ptrs], C.byref(nc), C.byref(nm), C.byref(ev))
+    if rc == -1:   # BWTMI_E_ARG: nothing was written
+        untouched = all(p.value is None for p in ptrs) and nc.value == -1 and nm.value == -1
+        msg = lib().bwtmi_last_error()
+        raise ValueError((msg.decode(errors="replace") if msg else "bad argument") +
+                         ("" if untouched else " [outputs were written]"))
+    check(rc)
+    try:
+        n, ng = nc.value, go.size - 1
+        names = ("chain_off", "score", "n_anchors", "qstart", "qend", "rstart", "rend", "member_off", "member")
+        kinds = (np.int64, np.int32, np.int32, np.int32, np.int32, np.int64, np.int64, np.int64, np.int64)
+        counts = (ng + 1, n, n, n, n, n, n, n + 1, nm.value)
+        out = {k: take(p, t, c) for k, p, t, c in zip(names, ptrs, kinds, counts)}
+        out["evals"] = ev.value
+        return out
+    finally:
+        for p in ptrs:
+            lib().bwtmi_free(p)
 
 
 # bwtmi_radix_sort kinds: name -> (code, key dtype, value dtype or None)

@@ -106,6 +106,46 @@ class SmemResult:
                 [self.positions[int(po[j]):int(po[j + 1])] for j in range(a, b)])
 
 
+class MapResult:
+    """Chains of BWTCore.map_batch: `offsets` (int64[nq + 1]) into `strand`
+    (uint8, 0 = '+', 1 = '-'), `score`, `n_anchors`, `qstart`, `qend` (int32),
+    `rstart`, `rend` (int64); `member_offsets` (int64[nchain + 1]) into the
+    chains' anchors `member_q`, `member_len` (int32) and `member_r` (int64).
+    Query coordinates are the original query's on both strands.  result[i] =
+    (strand, score, n_anchors, qstart, qend, rstart, rend, anchors per chain as
+    int64[k, 3] rows (q, r, len)) of query i, its chains by strand, then in the
+    chainer's order.  `positions_total` is the SMEM step's position count (what
+    max_positions caps), `anchors` the anchors chained, `skipped_smems` the SMEMs
+    above max_occ (no anchors), `evals` the predecessors the DP evaluated."""
+
+    __slots__ = ("offsets", "strand", "score", "n_anchors", "qstart", "qend", "rstart", "rend", "member_offsets",
+                 "member_q", "member_r", "member_len", "positions_total", "skipped_smems", "anchors", "evals")
+
+    def __init__(self, offsets, strand, score, n_anchors, qstart, qend, rstart, rend, member_offsets, member_q,
+                 member_r, member_len, positions_total=0, skipped_smems=0, anchors=0, evals=0):
+        self.offsets, self.strand, self.score, self.n_anchors = offsets, strand, score, n_anchors
+        self.qstart, self.qend, self.rstart, self.rend = qstart, qend, rstart, rend
+        self.member_offsets, self.member_q, self.member_r, self.member_len = member_offsets, member_q, member_r, member_len
+        self.positions_total, self.skipped_smems, self.anchors, self.evals = positions_total, skipped_smems, anchors, evals
+
+    def __len__(self):
+        return self.offsets.size - 1
+
+    def members(self, k: int) -> np.ndarray:
+        """The anchors of chain k: int64[n, 3] rows (q, r, len), in chain order."""
+        a, b = int(self.member_offsets[k]), int(self.member_offsets[k + 1])
+        return np.stack([self.member_q[a:b].astype(np.int64), self.member_r[a:b],
+                         self.member_len[a:b].astype(np.int64)], axis=1)
+
+    def __getitem__(self, i: int):
+        if not -len(self) <= i < len(self):
+            raise IndexError(i)
+        i %= len(self)
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        return (self.strand[a:b], self.score[a:b], self.n_anchors[a:b], self.qstart[a:b], self.qend[a:b],
+                self.rstart[a:b], self.rend[a:b], [self.members(k) for k in range(a, b)])
+
+
 class BWTCore:
     BASE_TO_BITS = {"A": 0, "C": 1, "G": 2, "T": 3, "N": 0}
     BITS_TO_BASE = {0: "A", 1: "C", 2: "G", 3: "T"}
@@ -393,6 +433,56 @@ class BWTCore:
             return SmemResult(take(ptrs[0], np.int64, nq + 1), take(ptrs[1], np.int32, n), take(ptrs[2], np.int32, n),
                               take(ptrs[3], np.uint8, n), take(ptrs[4], np.int64, n), take(ptrs[5], np.int64, n + 1),
                               take(ptrs[6], np.int64, npos.value), total.value, work.value, steps.value)
+        finally:
+            for p in ptrs:
+                lib().bwtmi_free(p)
+
+    def chain_anchors(self, group_off, q, r, length, **chain_params) -> dict:
+        """The device chainer on a caller's anchors (include/bwtmi.h,
+        bwtmi_chain_anchors, states the contract): see bwtmi._lib.chain_anchors."""
+        return _lib.chain_anchors(self._ctx, group_off, q, r, length, **chain_params)
+
+    def map_batch(self, queries: Sequence[Union[str, bytes]], min_len: int = 19, both_strands: bool = False,
+                  long: bool = False, max_occ: Optional[int] = None, max_positions: Optional[int] = None,
+                  **chain_params) -> "MapResult":
+        """Where every query lies in the index text: its SMEMs (smem_batch, or
+        smem_long_batch with long=True, which needs reverse_index=True) turned
+        into anchors and chained on the device (include/bwtmi.h,
+        bwtmi_index_map_batch, states the contract).  chain_params: max_gap,
+        bandwidth, max_pred, min_score, min_anchors (absent: the defaults 5000,
+        500, 1024, 40, 1).  ValueError as smem_batch raises it, and for
+        max_pred > 4096 or bandwidth > max_gap; BwtmiError with the position
+        count when it exceeds max_positions, and for long=True without a
+        reverse index."""
+        for name, v in (("max_occ", max_occ), ("max_positions", max_positions)):
+            if v is not None and int(v) <= 0:
+                raise ValueError(f"{name} must be positive")
+        cp = _lib.chain_params(**chain_params)
+        enc = [q.encode("utf-8") if isinstance(q, str) else bytes(q) for q in queries]
+        off = np.zeros(len(enc) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(e) for e in enc]) if enc else 0
+        blob = np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8)
+        nq = off.size - 1
+        ptrs = [C.c_void_p() for _ in range(12)]
+        nc, nm, total, skipped, anchors, evals = (C.c_int64(0) for _ in range(6))
+        rc = lib().bwtmi_index_map_batch(self._ctx, self._h, blob.ctypes.data_as(C.c_void_p),
+                                         off.ctypes.data_as(C.c_void_p), nq, int(min_len),
+                                         (1 if both_strands else 0) | (4 if long else 0),
+                                         0 if max_occ is None else int(max_occ),
+                                         0 if max_positions is None else int(max_positions), C.byref(cp),
+                                         *[C.byref(p) for p in ptrs], C.byref(nc), C.byref(nm), C.byref(total),
+                                         C.byref(skipped), C.byref(anchors), C.byref(evals))
+        if rc == -1:   # BWTMI_E_ARG
+            msg = lib().bwtmi_last_error()
+            raise ValueError(msg.decode(errors="replace") if msg else "bad argument")
+        check(rc)
+        try:
+            n, m = nc.value, nm.value
+            kinds = (np.int64, np.uint8, np.int32, np.int32, np.int32, np.int32, np.int64, np.int64, np.int64, np.int32,
+                     np.int64, np.int32)
+            counts = (nq + 1, n, n, n, n, n, n, n, n + 1, m, m, m)
+            return MapResult(*[_lib.take(p, t, k) for p, t, k in zip(ptrs, kinds, counts)], total.value, skipped.value,
+                             anchors.value, evals.value)
         finally:
             for p in ptrs:
                 lib().bwtmi_free(p)

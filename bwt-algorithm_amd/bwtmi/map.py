@@ -1,0 +1,108 @@
+"""`map.py` command line: where reads lie in a genome, and how much longer or
+shorter they are there -- the SMEM seeds of `seeds.py` chained on the device,
+one PAF row per chain.
+
+    python map.py IN.fa QUERIES [-l MIN_LEN] [--both-strands] [--long] [--max-occ N] [--max-gap N]
+                  [--bandwidth N] [--min-score N] [--min-anchors N] -o OUT.paf
+
+QUERIES is in the pattern-file format of `locate.py` (`SEQ` or `NAME<TAB>SEQ`
+per line).  One FM index per contig (seq + '$', built on the device, released
+before the next; with `--long` also its reverse index, for reads up to
+1,048,576 bp instead of 1024), one BWTCore.map_batch per contig.  Rows are
+ordered by contig, then query order in the file, then the result's order
+(strand, then the chainer's: best chain first).  The 12 PAF columns are
+`qname qlen qstart qend strand tname tlen tstart tend nmatch alen 255`: tlen is
+the contig's length without the '$', nmatch = len_0 + the sum of min(len_i, dq,
+dr) along the chain (the bases its anchors cover, overlaps counted once), alen
+= max(qend - qstart, tend - tstart).  Tags: `s1:i:` the chain's score, `cm:i:`
+its anchors, `dl:i:` = (last qe - first qe) - (last re - first re) over the
+chain's anchors in the searched string's coordinates: positive when the read
+is longer than the reference there -- through both flanks of a tandem repeat,
+the tract's length difference.  Chains are per contig: each contig has its own
+index.  Not in the reference: `bwt.py` stays the drop-in, this tool stands next
+to it.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from typing import List, Optional, Sequence
+
+from .locate import parse_patterns
+
+
+def map_rows(chrom: str, tlen: int, names: Sequence[str], qlens: Sequence[int], res) -> List[str]:
+    """PAF rows of one contig's chains (`res`: the arrays of a MapResult), in
+    the result's order: query order, then strand, then the chainer's order."""
+    off = [int(v) for v in res.offsets]
+    mo = [int(v) for v in res.member_offsets]
+    rows = []
+    for q in range(len(off) - 1):
+        m = int(qlens[q])
+        for k in range(off[q], off[q + 1]):
+            rev = bool(int(res.strand[k]))
+            a, b = mo[k], mo[k + 1]
+            ln = [int(v) for v in res.member_len[a:b]]
+            # ends in the searched string's coordinates (revcomp(Q) on strand '-')
+            qe = [(m - int(v)) if rev else int(v) + l for v, l in zip(res.member_q[a:b], ln)]
+            re = [int(v) + l for v, l in zip(res.member_r[a:b], ln)]
+            nmatch = ln[0] + sum(min(ln[i], qe[i] - qe[i - 1], re[i] - re[i - 1]) for i in range(1, b - a))
+            dl = (qe[-1] - qe[0]) - (re[-1] - re[0])
+            qs, qend, ts, te = int(res.qstart[k]), int(res.qend[k]), int(res.rstart[k]), int(res.rend[k])
+            rows.append(f"{names[q]}\t{m}\t{qs}\t{qend}\t{'-' if rev else '+'}\t{chrom}\t{tlen}\t{ts}\t{te}\t{nmatch}\t"
+                        f"{max(qend - qs, te - ts)}\t255\ts1:i:{int(res.score[k])}\tcm:i:{int(res.n_anchors[k])}\t"
+                        f"dl:i:{dl}\n")
+    return rows
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Map reads to a genome: chained SMEM seeds as PAF (MI355X-native FM index)")
+    p.add_argument("reference", help="Reference genome FASTA file")
+    p.add_argument("queries", help="Query file: one SEQ or NAME<TAB>SEQ per line ('#' comments), up to 1024 bp each "
+                                   "(1,048,576 with --long)")
+    p.add_argument("-l", "--min-len", type=int, default=19, help="Shortest SMEM used as a seed (default: 19)")
+    p.add_argument("--both-strands", action="store_true", help="Also map the reverse complement")
+    p.add_argument("--long", action="store_true",
+                   help="Long reads: build each contig's reverse index too and lift the 1024 bp limit to 1,048,576 bp")
+    p.add_argument("--max-occ", type=int, default=1024,
+                   help="Seeds with more occurrences than this give no anchors (default: 1024)")
+    p.add_argument("--max-gap", type=int, default=None, help="Longest gap between chained anchors (default: 5000)")
+    p.add_argument("--bandwidth", type=int, default=None,
+                   help="Largest difference between the query and reference gaps (default: 500)")
+    p.add_argument("--min-score", type=int, default=None, help="Lowest chain score reported (default: 40)")
+    p.add_argument("--min-anchors", type=int, default=None, help="Fewest anchors of a reported chain (default: 1)")
+    p.add_argument("-o", "--output", required=True, help="Output PAF file")
+    return p
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    a = build_parser().parse_args(argv)
+    tmp = a.output + ".tmp"
+    try:
+        with open(a.queries) as fh:
+            pats = parse_patterns(fh)
+        from .core import BWTCore
+        from .records import Job
+        names, seqs = [n for n, _ in pats], [s for _, s in pats]
+        qlens = [len(s.encode("utf-8")) for s in seqs]
+        job = Job()
+        job.load_fasta(a.reference, 0)
+        with open(tmp, "w") as out:
+            for cid in range(job.contig_count()):
+                chrom = job.contig_info(cid)[0]
+                seq = job.contig_seq(cid)
+                core = BWTCore(seq + b"$", build_kmer=False, reverse_index=a.long)
+                try:
+                    res = core.map_batch(seqs, a.min_len, a.both_strands, a.long, a.max_occ, None, max_gap=a.max_gap,
+                                         bandwidth=a.bandwidth, min_score=a.min_score, min_anchors=a.min_anchors)
+                finally:
+                    core.clear()
+                out.writelines(map_rows(chrom, len(seq), names, qlens, res))
+        os.replace(tmp, a.output)
+    except (ValueError, RuntimeError, OSError) as e:   # a bad query or parameter, a tripped cap, an unreadable file
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        print(f"map: {e}", file=sys.stderr)
+        return 1
+    return 0

@@ -782,6 +782,110 @@ int bwtmi_index_smem_long_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t 
                       pos_off, pos, nsmem, npos, positions_total, work, steps, index_smem_long_batch);
 }
 
+// ------------------------------------------------------------ chaining
+// the caller's parameters with the defaults filled in, checked
+static ChainParams chain_params(const bwtmi_chain_params *p) {
+    ChainParams r;
+    if (!p) return r;
+    CHECK_ARG(p->reserved[0] == 0 && p->reserved[1] == 0 && p->reserved[2] == 0, "chain: reserved fields must be 0");
+    if (p->max_gap > 0) r.max_gap = p->max_gap;
+    if (p->bandwidth > 0) r.bandwidth = p->bandwidth;
+    if (p->max_pred > 0) r.max_pred = p->max_pred;
+    if (p->min_score > 0) r.min_score = p->min_score;
+    if (p->min_anchors > 0) r.min_anchors = p->min_anchors;
+    if (r.max_pred > 4096) fail(BWTMI_E_ARG, "chain: max_pred %d is above 4096", (int)r.max_pred);
+    if (r.bandwidth > r.max_gap)
+        fail(BWTMI_E_ARG, "chain: bandwidth %d is above max_gap %d", (int)r.bandwidth, (int)r.max_gap);
+    return r;
+}
+
+int bwtmi_chain_anchors(bwtmi_ctx *ctx, const int64_t *group_off, int64_t ng, const int32_t *q, const int64_t *r,
+                        const int32_t *len, const bwtmi_chain_params *params, int64_t **chain_off, int32_t **score,
+                        int32_t **n_anchors, int32_t **qstart, int32_t **qend, int64_t **rstart, int64_t **rend,
+                        int64_t **member_off, int64_t **member, int64_t *nchain, int64_t *nmember, int64_t *evals) {
+    return guard([&] {
+        CHECK_ARG(ctx && group_off && ng >= 0 && chain_off && score && n_anchors && qstart && qend && rstart && rend &&
+                      member_off && member && nchain && nmember,
+                  "bad argument");
+        const ChainParams p = chain_params(params);
+        CHECK_ARG(group_off[0] == 0, "chain: group_off[0] must be 0");
+        for (int64_t g = 0; g < ng; ++g)
+            if (group_off[g + 1] < group_off[g])
+                fail(BWTMI_E_ARG, "chain: group_off decreases at group %lld", (long long)g);
+        const int64_t na = group_off[ng];
+        CHECK_ARG(na == 0 || (q && r && len), "chain: null anchor array");
+        for (int64_t i = 0; i < na; ++i)
+            if (len[i] < 1 || q[i] < 0 || r[i] < 0 || (int64_t)q[i] + len[i] > (int64_t{1} << 24) ||
+                r[i] + len[i] > (int64_t{1} << 32))
+                fail(BWTMI_E_ARG, "chain: anchor %lld (q %d, r %lld, len %d) outside len >= 1, 0 <= q, q + len <= 2^24, "
+                     "0 <= r, r + len <= 2^32", (long long)i, (int)q[i], (long long)r[i], (int)len[i]);
+        ChainResult res;
+        chain_anchors_device(use(ctx->c), group_off, ng, q, r, len, p, res);
+        *chain_off = malloc_copy(res.chain_off);
+        *score = malloc_copy(res.score);
+        *n_anchors = malloc_copy(res.n_anchors);
+        *qstart = malloc_copy(res.qstart);
+        *qend = malloc_copy(res.qend);
+        *rstart = malloc_copy(res.rstart);
+        *rend = malloc_copy(res.rend);
+        *member_off = malloc_copy(res.member_off);
+        *member = malloc_copy(res.member);
+        *nchain = (int64_t)res.score.size();
+        *nmember = (int64_t)res.member.size();
+        if (evals) *evals = res.evals;
+    });
+}
+
+int bwtmi_index_map_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                          int32_t min_len, uint32_t flags, int64_t max_occ, int64_t max_positions,
+                          const bwtmi_chain_params *params, int64_t **chain_off, uint8_t **strand, int32_t **score,
+                          int32_t **n_anchors, int32_t **qstart, int32_t **qend, int64_t **rstart, int64_t **rend,
+                          int64_t **member_off, int32_t **member_q, int64_t **member_r, int32_t **member_len,
+                          int64_t *nchain, int64_t *nmember, int64_t *positions_total, int64_t *skipped_smems,
+                          int64_t *anchors, int64_t *evals) {
+    return guard([&] {
+        CHECK_ARG(ctx && idx && off && nq >= 0 && chain_off && strand && score && n_anchors && qstart && qend && rstart &&
+                      rend && member_off && member_q && member_r && member_len && nchain && nmember,
+                  "bad argument");
+        CHECK_ARG(qs || nq == 0, "null queries");
+        *chain_off = *rstart = *rend = *member_off = *member_r = nullptr;
+        *score = *n_anchors = *qstart = *qend = *member_q = *member_len = nullptr;
+        *strand = nullptr;
+        *nchain = *nmember = 0;
+        for (int64_t *v : {positions_total, skipped_smems, anchors, evals})
+            if (v) *v = 0;
+        CHECK_ARG((flags & ~(BWTMI_SMEM_BOTH_STRANDS | BWTMI_MAP_LONG)) == 0, "unknown map flag");
+        const ChainParams p = chain_params(params);
+        Ctx &c = use(ctx->c);
+        MapResult r;
+        try {
+            index_map_batch(c, idx->d, qs, off, nq, min_len, (flags & BWTMI_SMEM_BOTH_STRANDS) != 0,
+                            (flags & BWTMI_MAP_LONG) != 0, max_occ, max_positions, p, r);
+        } catch (...) {
+            if (positions_total) *positions_total = r.positions_total;   // the count a tripped cap reports
+            throw;
+        }
+        if (positions_total) *positions_total = r.positions_total;
+        if (skipped_smems) *skipped_smems = r.skipped_smems;
+        if (anchors) *anchors = r.anchors;
+        if (evals) *evals = r.evals;
+        *chain_off = malloc_copy(r.chain_off);
+        *strand = malloc_copy(r.strand);
+        *score = malloc_copy(r.score);
+        *n_anchors = malloc_copy(r.n_anchors);
+        *qstart = malloc_copy(r.qstart);
+        *qend = malloc_copy(r.qend);
+        *rstart = malloc_copy(r.rstart);
+        *rend = malloc_copy(r.rend);
+        *member_off = malloc_copy(r.member_off);
+        *member_q = malloc_copy(r.mq);
+        *member_r = malloc_copy(r.mr);
+        *member_len = malloc_copy(r.mlen);
+        *nchain = (int64_t)r.score.size();
+        *nmember = (int64_t)r.mq.size();
+    });
+}
+
 static LibParams lib_params(const bwtmi_lib_params *p) {
     LibParams q;
     if (p) {

@@ -317,6 +317,19 @@ __device__ __forceinline__ int64_t xcd_tile(int64_t b, int64_t ntiles) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
 }
 
+// The interval that owns element t of a scanned offset array of `count`
+// intervals, at(0) <= t < at(count): the lo with at(lo) <= t < at(lo + 1)
+template <class At>
+__device__ __forceinline__ int64_t owner_of(int64_t count, int64_t t, At at) {
+    int64_t lo = 0, hi = count;   // at(lo) <= t < at(hi)
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (at(mid) <= t) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // one stable 8-bit pass at `shift` from (kin, vin) into (kout, vout)
 void radix_pass_k32(Ctx &c, const uint32_t *kin, const uint32_t *vin, uint32_t *kout, uint32_t *vout, int64_t n,
                     int shift);
@@ -479,5 +492,34 @@ void index_smem_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t 
 void index_smem_long_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq,
                            int32_t min_len, bool both_strands, int64_t max_occ, int64_t max_positions,
                            SmemResult &out);
+
+// ----- colinear chaining of anchors, and read mapping over it (chain.hip; contracts in bwtmi.h)
+struct ChainParams {   // resolved: every field holds its value, not "<= 0: the default"
+    int32_t max_gap = 5000, bandwidth = 500, max_pred = 1024, min_score = 40, min_anchors = 1;
+};
+struct ChainResult {
+    std::vector<int64_t> chain_off;                        // ng + 1
+    std::vector<int32_t> score, n_anchors, qstart, qend;   // per chain
+    std::vector<int64_t> rstart, rend;
+    std::vector<int64_t> member_off, member;               // nchain + 1 offsets; input indices of the anchors
+    int64_t evals = 0;                                     // predecessors the DP evaluated
+};
+// group g = anchors [group_off[g], group_off[g + 1]) of q / r / len (host arrays, validated by the caller)
+void chain_anchors_device(Ctx &c, const int64_t *group_off, int64_t ng, const int32_t *q, const int64_t *r,
+                          const int32_t *len, const ChainParams &p, ChainResult &out);
+struct MapResult {
+    std::vector<int64_t> chain_off;                        // nq + 1
+    std::vector<uint8_t> strand;                           // per chain
+    std::vector<int32_t> score, n_anchors, qstart, qend;
+    std::vector<int64_t> rstart, rend;
+    std::vector<int64_t> member_off;                       // nchain + 1 offsets into the three member columns
+    std::vector<int32_t> mq, mlen;
+    std::vector<int64_t> mr;
+    int64_t positions_total = 0;                           // the SMEM step's position count
+    int64_t anchors = 0, skipped_smems = 0, evals = 0;
+};
+void index_map_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq, int32_t min_len,
+                     bool both_strands, bool long_entry, int64_t max_occ, int64_t max_positions, const ChainParams &p,
+                     MapResult &out);
 
 }  // namespace bwtmi

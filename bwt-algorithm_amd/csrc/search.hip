@@ -223,19 +223,6 @@ void with_rank(Ctx &c, const DeviceIndex *ix, Launch &&launch, int place = 0) {
     else launch(fm_view(c, ix, place));
 }
 
-// The interval that owns element t of a scanned offset array of `count`
-// intervals, at(0) <= t < at(count): the lo with at(lo) <= t < at(lo + 1)
-template <class At>
-__device__ __forceinline__ int64_t owner_of(int64_t count, int64_t t, At at) {
-    int64_t lo = 0, hi = count;   // at(lo) <= t < at(hi)
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (at(mid) <= t) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 inline uint8_t comp_byte(uint8_t ch) {
     switch (ch) {
         case 'A': return 'T';

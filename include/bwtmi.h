@@ -393,6 +393,102 @@ int bwtmi_index_smem_long_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t 
                                 int64_t **count, int64_t **pos_off, int64_t **pos, int64_t *nsmem, int64_t *npos,
                                 int64_t *positions_total, int64_t *work, int64_t *steps);
 
+/* ------------------------------------------------------------ chaining and read mapping
+ * Colinear chaining of anchors (not in the reference): the step from a bag of
+ * seeds to "where does this read lie, and how much longer or shorter is it
+ * there than the text".
+ *   anchor   (q, r, len), len >= 1: query bytes [q, q + len) equal text bytes
+ *            [r, r + len).  qe = q + len, re = r + len.
+ *   groups   anchors come in groups, group g = anchors [group_off[g],
+ *            group_off[g + 1]); chaining never crosses a group.
+ *   order    inside a group the anchors are ordered by (re, qe) ascending, ties
+ *            in input order; the indices 0 .. A - 1 below are in this order.
+ *   DP       all in integers:
+ *              cost(d) = 0 if d == 0 else (d >> 4) + (bit_length(d) >> 1)
+ *              f[i] = len_i; p[i] = -1
+ *              for j = i - 1 down to max(0, i - max_pred):
+ *                  dr = re_i - re_j;  if dr > max_gap: break
+ *                  dq = qe_i - qe_j
+ *                  if dq <= 0 or dr <= 0 or dq > max_gap: continue
+ *                  d = |dr - dq|;     if d > bandwidth: continue
+ *                  s = f[j] + min(len_i, dq, dr) - cost(d)
+ *                  if s > f[i]: f[i], p[i] = s, j
+ *            (strict: of predecessors with equal s the nearest, largest j, wins;
+ *            the order is by re, so after the break nothing further qualifies).
+ *   chains   per group: visit the anchors by (f descending, index ascending);
+ *            skip a used anchor; otherwise walk i, p[i], p[p[i]], ... marking
+ *            each anchor used, and stop at p = -1 or in front of an anchor u that
+ *            is already used.  score = f[i] - (f[u] if the walk stopped at u else
+ *            0).  The chain is kept when score >= min_score and it has at least
+ *            min_anchors anchors; the marks stay either way.  A group's chains
+ *            come out in visiting order.
+ *   fields   of a chain: score, n_anchors, qstart = the minimum q of its
+ *            anchors, qend = the maximum qe, rstart = the minimum r, rend = the
+ *            maximum re, and its anchors in ascending index order.
+ *   params   each field <= 0: the default -- max_gap 5000, bandwidth 500,
+ *            max_pred 1024, min_score 40, min_anchors 1.  The defaults are
+ *            choices (round numbers in the range read mappers use for reads of
+ *            10^2..10^4 bytes), not measurements.  BWTMI_E_ARG before anything
+ *            reaches the device: max_pred > 4096, bandwidth > max_gap (after
+ *            the defaults), a nonzero reserved field.  params = NULL: all
+ *            defaults. */
+typedef struct {
+    int32_t max_gap, bandwidth, max_pred, min_score, min_anchors, reserved[3];
+} bwtmi_chain_params;
+/* The device chainer (chain.hip) on a caller's anchors, exactly as
+ * bwtmi_index_map_batch runs it (tests, embedders).
+ *   in       group_off[ng + 1] (group_off[0] = 0), q / r / len[group_off[ng]].
+ *   out      chain_off[ng + 1]: the groups' offsets into the chain arrays score,
+ *            n_anchors, qstart, qend (int32), rstart, rend (int64), *nchain rows;
+ *            member_off[*nchain + 1] into member[*nmember]: the input indices of
+ *            each chain's anchors, in chain order.  All nine are malloc'd (never
+ *            NULL on success; free with bwtmi_free).  *evals (may be NULL): the
+ *            predecessors the DP evaluated, i.e. the j it reached before a break.
+ *   errors   BWTMI_E_ARG with every output untouched: the parameter errors
+ *            above, ng < 0, group_off[0] != 0 or decreasing offsets, len < 1,
+ *            q < 0 or qe > 2^24, r < 0 or re > 2^32, a null anchor array with
+ *            anchors present.  BWTMI_E_NOMEM: 2^31 anchors or groups and more.
+ *            ng = 0 and empty groups are legal. */
+int bwtmi_chain_anchors(bwtmi_ctx *ctx, const int64_t *group_off, int64_t ng, const int32_t *q, const int64_t *r,
+                        const int32_t *len, const bwtmi_chain_params *params, int64_t **chain_off, int32_t **score,
+                        int32_t **n_anchors, int32_t **qstart, int32_t **qend, int64_t **rstart, int64_t **rend,
+                        int64_t **member_off, int64_t **member, int64_t *nchain, int64_t *nmember, int64_t *evals);
+/* Batched read mapping: the SMEMs of every query (bwtmi_index_smem_batch's
+ * arguments and search; with BWTMI_MAP_LONG bwtmi_index_smem_long_batch's, which
+ * needs BWTMI_INDEX_REVERSE, else BWTMI_E_STATE, and lifts the 1024-byte limit
+ * to 1,048,576), chained on the device.
+ *   groups   one per searched string, that is (query, strand).
+ *   anchors  one per listed position of every SMEM with count <= max_occ: for
+ *            the SMEM [s, e) of the searched string (Q, or revcomp(Q) on strand
+ *            1) at text position pos, (q, r, len) = (s, pos, e - s).  An SMEM
+ *            above max_occ gives no anchors; *skipped_smems counts them.  The
+ *            anchor count is the SMEM step's position count and max_positions
+ *            caps it exactly as there (BWTMI_E_NOMEM, nothing truncated,
+ *            *positions_total either way).
+ *   out      chain_off[nq + 1]: the queries' offsets into strand (uint8), score,
+ *            n_anchors, qstart, qend (int32), rstart, rend (int64); member_off
+ *            [*nchain + 1] into the members' member_q, member_r, member_len.
+ *            Query coordinates (qstart, qend, member_q) are the original
+ *            query's on both strands, [m - e', m - s') for [s', e') of revcomp(Q):
+ *            as SMEMs are reported, and PAF's convention.  A strand-1 chain's
+ *            members still come in the chain's order, so their member_q descend.
+ *   order    queries in batch order; a query's chains by strand, then in the
+ *            chainer's visiting order.
+ *   counts   (each may be NULL) *positions_total, *skipped_smems, *anchors,
+ *            *evals (the DP's evaluated predecessors).
+ *   errors   those of the SMEM entry chosen, the parameter errors above, an
+ *            unknown flag; every output pointer is then NULL and every count 0
+ *            (positions_total excepted, as above).
+ * The twelve arrays are malloc'd (never NULL on success; free with bwtmi_free). */
+#define BWTMI_MAP_LONG 4u
+int bwtmi_index_map_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                          int32_t min_len, uint32_t flags, int64_t max_occ, int64_t max_positions,
+                          const bwtmi_chain_params *params, int64_t **chain_off, uint8_t **strand, int32_t **score,
+                          int32_t **n_anchors, int32_t **qstart, int32_t **qend, int64_t **rstart, int64_t **rend,
+                          int64_t **member_off, int32_t **member_q, int64_t **member_r, int32_t **member_len,
+                          int64_t *nchain, int64_t *nmember, int64_t *positions_total, int64_t *skipped_smems,
+                          int64_t *anchors, int64_t *evals);
+
 /* ------------------------------------------------------------ repeat job
  * Replaces the per-contig worker result handling and the post-processing of
  * TandemRepeatFinder (bwt.py:3040-3141, 3402-3944) and save_results with
