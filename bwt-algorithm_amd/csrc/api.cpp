@@ -923,7 +923,7 @@ int bwtmi_index_short_imperfect(bwtmi_ctx *ctx, bwtmi_index *idx, const bwtmi_li
                   "the job contig must hold the index text");
         use(ctx->c);
         std::vector<int64_t> sp(seen, seen + 2 * nseen);
-        short_imperfect_device(ctx->c, idx->d, lib_params(p), sp, contig_id, job->j.final_recs);
+        short_imperfect_device(ctx->c, idx->d, lib_params(p), sp, contig_id, job->j.recs_own());
         job->j.postprocessed = true;
     });
 }
@@ -946,7 +946,8 @@ int bwtmi_index_tier3(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *reads, co
             auto &dst = J.t3[(size_t)contig_id];
             for (auto &r : recs) dst.push_back(std::move(r));
         } else {
-            for (auto &r : recs) J.final_recs.push_back(std::move(r));
+            RecVec &fin = J.recs_own();
+            for (auto &r : recs) fin.push_back(std::move(r));
             J.postprocessed = true;
         }
     });
@@ -960,7 +961,7 @@ int bwtmi_index_long_repeats(bwtmi_ctx *ctx, bwtmi_index *idx, const bwtmi_lib_p
         CHECK_ARG(p->min_copies >= 0 && p->min_array_length >= 0, "bad parameters");
         use(ctx->c);
         std::vector<int64_t> sp(seen, seen + 2 * nseen);
-        simple_scan_device(ctx->c, idx->d, lib_params(p), sp, contig_id, job->j.final_recs);
+        simple_scan_device(ctx->c, idx->d, lib_params(p), sp, contig_id, job->j.recs_own());
         job->j.postprocessed = true;
     });
 }
@@ -976,7 +977,7 @@ int bwtmi_job_tier1(bwtmi_ctx *ctx, bwtmi_job *job, int32_t contig_id, int32_t m
         const int64_t n = (int64_t)full.size();
         upload_text(c, c.slot[S_TEXT], (const uint8_t *)full.data(), n);
         tier1_device(c, c.slot[S_TEXT].as<uint8_t>(), (const uint8_t *)full.data(), n, max_motif_length, contig_id,
-                     job->j.final_recs);
+                     job->j.recs_own());
         job->j.postprocessed = true;
     });
 }
@@ -1011,6 +1012,7 @@ int bwtmi_job_add_contig(bwtmi_job *job, const char *name, const uint8_t *full, 
         CHECK_ARG(job && name && (full || full_len == 0) && full_len >= 0, "bad argument");
         TEXT_JOIN(job);
         CHECK_ARG(trim_left >= 0 && trim_right >= 0 && trim_left + trim_right <= full_len, "bad trim");
+        job->j.recs_own();   // a new contig may renumber the fold units the survivors are kept by
         Contig c;
         c.name = name;
         c.full.assign((const char *)full, (size_t)full_len);
@@ -1332,12 +1334,7 @@ int bwtmi_job_reset(bwtmi_job *job) {
         job->j.screened.clear();
         job->j.shits.clear();
         job->j.raw_n.clear();
-        {   // the last records are released on the background reaper thread,
-            // behind the next step's device phase
-            auto old = std::make_shared<RecVec>();
-            old->swap(job->j.final_recs);
-            defer([old] { RecVec().swap(*old); });
-        }
+        job->j.drop_results();   // released on the background reaper thread, behind the next step's device phase
         job->j.t3.clear();
         job->j.postprocessed = false;
     });
@@ -1390,7 +1387,7 @@ ScanPlan scan_plan(bwtmi_job *job) {
     J.shits.assign(J.contigs.size(), {});
     J.raw_n.assign(J.contigs.size(), 0);
     J.errors.assign(J.contigs.size(), std::string());
-    J.final_recs.clear();
+    J.drop_results();
     J.postprocessed = false;
     ScanPlan plan;
     const bwtmi_params &P = J.params;
@@ -1623,7 +1620,7 @@ int bwtmi_job_postprocess(bwtmi_job *job) {
     });
 }
 
-int64_t bwtmi_job_count(const bwtmi_job *job) { return job ? (int64_t)job->j.final_recs.size() : -1; }
+int64_t bwtmi_job_count(const bwtmi_job *job) { return job ? (int64_t)job->j.count() : -1; }
 
 int bwtmi_job_render(bwtmi_job *job, int fmt, char **out, int64_t *len) {
     return guard([&] {
@@ -1692,7 +1689,11 @@ int bwtmi_job_unit_rows(bwtmi_job *job, int64_t *unit_rows) {
         Job &J = job->j;
         J.assign_units();
         for (int32_t u = 0; u < J.nunits; ++u) unit_rows[u] = 0;
-        for (const Rec &r : J.final_recs) ++unit_rows[J.contigs[(size_t)r.chrom].unit];
+        if (const std::shared_ptr<Survivors> sv = J.survivors()) {   // they know their units
+            for (size_t k = 0; k < sv->units(); ++k) unit_rows[sv->unit_id(k)] = (int64_t)sv->unit_size(k);
+            return;
+        }
+        for (const Rec &r : J.recs()) ++unit_rows[J.contigs[(size_t)r.chrom].unit];
     });
 }
 
@@ -1774,7 +1775,7 @@ int bwtmi_job_get_records(bwtmi_job *job, int64_t *ints9, double *dbls5) {
         CHECK_ARG(job && ints9 && dbls5, "null argument");
         TEXT_JOIN(job);
         size_t k = 0;
-        for (const Rec &r : job->j.final_recs) {
+        for (const Rec &r : job->j.recs()) {
             int64_t *I = ints9 + 9 * k;
             double *D = dbls5 + 5 * k;
             I[0] = r.start; I[1] = r.end; I[2] = r.length; I[3] = r.tier; I[4] = r.n_eval; I[5] = r.max_mm;
@@ -1806,9 +1807,11 @@ bool rec_string(const bwtmi_job *job, const Rec &r, int which, std::string_view 
 }  // namespace
 
 int64_t bwtmi_job_get_string(bwtmi_job *job, int64_t i, int which, char *buf, int64_t cap) {
-    if (!job || i < 0 || i >= (int64_t)job->j.final_recs.size()) return -1;
+    if (!job || i < 0 || i >= (int64_t)job->j.count()) return -1;
     std::string_view s;
-    if (!rec_string(job, job->j.final_recs[(size_t)i], which, s)) return -1;
+    const Rec *r = nullptr;
+    if (guard([&] { r = &job->j.recs()[(size_t)i]; }) != BWTMI_OK) return -1;
+    if (!rec_string(job, *r, which, s)) return -1;
     if (buf && cap > 0) std::memcpy(buf, s.data(), std::min<size_t>((size_t)cap, s.size()));
     return (int64_t)s.size();
 }
@@ -1817,7 +1820,9 @@ int64_t bwtmi_job_get_strings(bwtmi_job *job, int which, char *buf, int64_t cap,
     if (!job || which < 0 || which > 4) return -1;
     int64_t tot = 0;
     std::string_view s;
-    const auto &recs = job->j.final_recs;
+    const RecVec *built = nullptr;
+    if (guard([&] { built = &job->j.recs(); }) != BWTMI_OK) return -1;
+    const RecVec &recs = *built;
     for (size_t i = 0; i < recs.size(); ++i) {
         if (offsets) offsets[i] = tot;
         rec_string(job, recs[i], which, s);
@@ -1849,9 +1854,10 @@ int bwtmi_job_export(bwtmi_job *job, uint8_t **buf, int64_t *len) {
         CHECK_ARG(job && buf && len, "null argument");
         TEXT_JOIN(job);
         std::string s;
-        const int64_t n = (int64_t)job->j.final_recs.size();
+        const RecVec &recs = job->j.recs();
+        const int64_t n = (int64_t)recs.size();
         s.append((const char *)&n, sizeof n);
-        for (const Rec &r : job->j.final_recs) {
+        for (const Rec &r : recs) {
             WireRec w{};
             w.chrom = r.chrom; w.tier = r.tier; w.start = r.start; w.end = r.end; w.length = r.length;
             w.max_mm = r.max_mm; w.n_eval = r.n_eval; w.score = r.score; w.act_off = r.act_off; w.act_len = r.act_len;
@@ -1873,6 +1879,7 @@ int bwtmi_job_export(bwtmi_job *job, uint8_t **buf, int64_t *len) {
 
 static void import_wire(bwtmi_job *job, const uint8_t *buf, int64_t len) {
     CHECK_ARG(job && buf && len >= 8, "bad argument");
+    RecVec &fin = job->j.recs_own();
     int64_t n;
     std::memcpy(&n, buf, 8);
     int64_t o = 8;
@@ -1898,13 +1905,13 @@ static void import_wire(bwtmi_job *job, const uint8_t *buf, int64_t len) {
         o += w.motif_len;
         r.variations.assign((const char *)buf + o, (size_t)w.var_len);
         o += w.var_len;
-        job->j.final_recs.push_back(std::move(r));
+        fin.push_back(std::move(r));
     }
     // keep the reference's global order (natural chrom, start, end; stable,
     // bwt.py:3184-3187, 4147): every unit arrives whole, in order
     Job &J = job->j;
     J.assign_units();
-    std::stable_sort(J.final_recs.begin(), J.final_recs.end(), [&](const Rec &a, const Rec &b) {
+    std::stable_sort(fin.begin(), fin.end(), [&](const Rec &a, const Rec &b) {
         const int32_t ua = J.contigs[(size_t)a.chrom].unit, ub = J.contigs[(size_t)b.chrom].unit;
         if (ua != ub) return ua < ub;
         if (a.start != b.start) return a.start < b.start;
@@ -1921,7 +1928,7 @@ int bwtmi_job_set_records(bwtmi_job *job, const uint8_t *buf, int64_t len) {
     return guard([&] {
         CHECK_ARG(job, "null argument");
         TEXT_JOIN(job);
-        job->j.final_recs.clear();
+        job->j.drop_results();
         import_wire(job, buf, len);
     });
 }

@@ -10,6 +10,7 @@
 #include <exception>
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -241,6 +242,40 @@ struct Rec {
 
 using RecVec = std::vector<Rec, BigAlloc<Rec>>;
 
+// What the compound rules and the five writers read of a record (render.cpp):
+// a view, built from a Rec or directly for a compound-stage piece.  The motif,
+// the variations and the actual sequence are bytes owned elsewhere (the
+// record's strings, the contig's text).
+struct RecRef {
+    int64_t start = 0, end = 0;
+    double copies = 0.0, pmatch = 0.0, pindel = 0.0, mismatch_rate = 0.0, confidence = 1.0;
+    int64_t n_eval = 0, max_mm = 0, score = 0;
+    const char *motif = nullptr, *var = nullptr, *act = nullptr;
+    int64_t act_len = 0;         // 0: no actual sequence
+    int32_t mlen = 0, vlen = 0;  // vlen 0: variations None
+    int32_t chrom = 0, tier = 2;
+    char strand = '+';
+    bool kmer_stats = false, stats_none = false;   // as in Rec
+};
+
+// The final records of the last postprocess as the fold left them (post.cpp
+// owns what is behind this): its survivors, a few dozen bytes each, with the
+// arenas their strings live in.  The writers read them through views; Recs are
+// built from them only when somebody asks for records (Job::recs).  Kept when
+// every fold unit with records is one contig, so that each unit is one run of
+// one chromosome in start order.
+struct Survivors {
+    virtual ~Survivors() = default;
+    virtual size_t size() const = 0;                  // final records
+    virtual size_t units() const = 0;                 // fold units with records, in unit order
+    virtual int32_t unit_id(size_t k) const = 0;
+    virtual int32_t unit_chrom(size_t k) const = 0;
+    virtual size_t unit_size(size_t k) const = 0;
+    virtual void span(size_t k, size_t i, int64_t &start, int64_t &end, int32_t &mlen) const = 0;
+    virtual RecRef view(size_t k, size_t i) const = 0;
+    virtual void materialize(RecVec &out, int nt) const = 0;   // every record, in order, into an empty `out`
+};
+
 // motif utilities (MotifUtils, bwt.py:675-1381)
 std::string min_rotation(const std::string &s);
 void canonical_stranded(const std::string &s, std::string &canon, char &strand);
@@ -371,7 +406,21 @@ struct Job {
     std::vector<ScreenedVec> shits;                  // per contig: those screened hits (hits[c] empty)
     std::vector<int64_t> raw_n;                      // raw strict hits per contig
     std::vector<std::string> errors;                 // per contig: the worker's error (empty = none)
-    RecVec final_recs;                               // after bwt.py:3940-3944
+    // The final records (after bwt.py:3940-3944): final_recs, or, while
+    // recs_pending, still only `surv` -- every reader but the writers goes
+    // through recs(), every mutation through recs_own() or drop_results().
+    // recs_mu guards surv, recs_pending and the building of final_recs: the
+    // readers (count, recs, survivors) may be called from several threads at once
+    RecVec final_recs;
+    std::shared_ptr<Survivors> surv;
+    bool recs_pending = false;
+    mutable std::mutex recs_mu;
+    RecVec &recs();         // built from the survivors on first use (any thread)
+    RecVec &recs_own();     // the same, and the survivors are released: final_recs is about to change
+    void drop_results();    // no records: both are released behind the caller
+    size_t count() const;   // final records, built or not
+    std::shared_ptr<Survivors> survivors() const;   // null when the job holds none
+    void keep_survivors(std::shared_ptr<Survivors> s);   // postprocess: the records are these, still to be built
     std::vector<RecVec> t3;                          // per contig: Tier 3 records (bwt.py:3918-3924), joined
                                                      // after the contig's strict hits before nested suppression
     std::vector<uint8_t> selected;                   // scan only these contigs (empty = all)
@@ -512,7 +561,7 @@ enum Knob {
     KN_RUNS_DENSE, KN_RUNS_UNTILED, KN_SA_SMALL, KN_SEG_LEVELS, KN_SCREEN_WIDE, KN_FM_BYTES, KN_LS_CAP,
     KN_HOST_SCREEN, KN_NO_PLAIN, KN_INDEX_LANES, KN_SCAN_LANES, KN_NO_AVX512, KN_POOL_SPIN_US,
     KN_UNIT_GROUP_THREADS, KN_STATS, KN_NUMA_BIND, KN_NUMA_SMT, KN_FAIL_MERGE_CHUNK, KN_HIST_S, KN_DEVICE_CHECKS,
-    KN_SCREEN_DROP, KN_FOLD_CUTS, KN_FOLD_CHUNK, KN_COUNT
+    KN_SCREEN_DROP, KN_FOLD_CUTS, KN_FOLD_CHUNK, KN_RENDER_CHUNK, KN_FAIL_MATERIALISE, KN_COUNT
 };
 // a roctx range for the lifetime of the object (trace.cpp); names "bwtmi:<stage>"
 struct StageRange {

@@ -242,6 +242,7 @@ void load_fasta(Job &job, const char *path, int32_t flank_trim, int32_t world, i
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     job.text_join();   // a deferred pass 2 of the previous load still writes the old buffers
+    job.recs_own();    // records still held as the fold's survivors read the text that is replaced here
     const int nt = host_threads(job.params);
     thread_local Seq data;   // the file image (kept for the next load)
     read_file(path, data, nt, dev);   // with a device: the image is copied up while it is read
@@ -679,6 +680,7 @@ void fasta_load_parts(Job &job, const char *path, int32_t flank_trim, int32_t wo
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     job.text_join();
+    job.recs_own();    // (as in load_fasta)
     const int nt = host_threads(job.params);
     struct Inst {
         int32_t contig;

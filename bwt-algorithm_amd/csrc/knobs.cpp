@@ -28,6 +28,7 @@ constexpr KnobDef kDefs[KN_COUNT] = {
     {"POOL_SPIN_US", -1},       {"UNIT_GROUP_THREADS", 4}, {"STATS", 0},        {"NUMA_BIND", 0},
     {"NUMA_SMT", 0},            {"FAIL_MERGE_CHUNK", -1}, {"HIST_S", 0},         {"DEVICE_CHECKS", 0},
     {"SCREEN_DROP", 1},         {"FOLD_CUTS", 1},        {"FOLD_CHUNK", 0},
+    {"RENDER_CHUNK", 0},       {"FAIL_MATERIALISE", 0},
 };
 
 

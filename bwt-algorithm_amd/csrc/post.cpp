@@ -1425,13 +1425,15 @@ void check_device_cuts(const UnitCtx &u, const ScreenedVec &sh, int nt) {
 // after its nominal start up to the first cut at or after its nominal end
 // (none in its range: nothing), and waits for the download of those records
 // only.
+// The survivors go to `out` in order, as Items: nobody on the path from a FASTA
+// to a file reads a Rec, so none is built here (SurvivorSet below).
 // `shift` is the unit's common trim offset, added when the survivors are
-// materialised: the (start, end) order is unchanged by it and collapse only
+// viewed or materialised: the (start, end) order is unchanged by it and collapse only
 // compares overlaps, lengths and motifs.  restore: the unit's contigs have
 // different trim offsets (one of them is <= 2 trim long, offset 0), so its
 // segment goes to full-sequence coordinates before the collapse, as in
 // bwt.py:3316-3325, and shift is 0; such a unit has several contigs, so no bits.
-void fold_cuts(UnitCtx u, Pools &pools, const CutSrc &src, int nt, int64_t shift, bool restore, RecVec &out, double *ms) {
+void fold_cuts(UnitCtx u, Pools &pools, const CutSrc &src, int nt, int64_t shift, bool restore, ItemVec &out, double *ms) {
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     const int64_t n = src.n;
@@ -1582,43 +1584,15 @@ void fold_cuts(UnitCtx u, Pools &pools, const CutSrc &src, int nt, int64_t shift
         }
     }
     const auto t1 = clk::now();
-    // the survivors materialised at their offsets.  Every slot is constructed
-    // whatever throws: a task whose materialize throws constructs the rest of
-    // its slots before it reports, and the tasks after it only construct
-    // theirs, so the vector's destructor never meets a raw slot.
+    // the tasks' survivors, in order, in one array
     BWTMI_STAGE("bwtmi:refine..filter");
     const int64_t KS = K + 1;
     std::vector<int64_t> cnt((size_t)KS + 1, 0);
     for (int64_t k = 0; k < KS; ++k) cnt[(size_t)k + 1] = cnt[(size_t)k] + (int64_t)surv[(size_t)k].size();
-    {
-        DeferConstruct raw;   // constructed below, in parallel
-        out.resize((size_t)cnt[(size_t)KS]);
-    }
-    static_assert(std::is_nothrow_default_constructible<Rec>::value, "Rec() must not throw");
-    std::atomic<bool> failed{false};
-    std::exception_ptr err;
-    std::mutex err_mu;
+    out.resize((size_t)cnt[(size_t)KS]);
     parallel_items(KS, nt, [&](int64_t t, int) {
-        const int64_t q1 = cnt[(size_t)t + 1];
-        int64_t o = cnt[(size_t)t];   // slots [cnt[t], o) are constructed
-        if (!failed.load(std::memory_order_relaxed)) {
-            try {
-                const std::vector<Item> &sv = surv[(size_t)t];
-                for (size_t j = 0; j < sv.size(); ++j) {
-                    if (j + 8 < sv.size() && sv[j + 8].xp) __builtin_prefetch(sv[j + 8].x());
-                    ::new ((void *)&out[(size_t)o]) Rec();
-                    ++o;
-                    materialize(u, sv[j], shift, out[(size_t)o - 1]);
-                }
-            } catch (...) {
-                failed.store(true, std::memory_order_relaxed);
-                std::lock_guard<std::mutex> lk(err_mu);
-                if (!err) err = std::current_exception();
-            }
-        }
-        for (; o < q1; ++o) ::new ((void *)&out[(size_t)o]) Rec();
+        std::copy(surv[(size_t)t].begin(), surv[(size_t)t].end(), out.begin() + (std::ptrdiff_t)cnt[(size_t)t]);
     });
-    if (err) std::rethrow_exception(err);
     const auto t2 = clk::now();
     auto d = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     if (stats_on()) {
@@ -1626,23 +1600,34 @@ void fold_cuts(UnitCtx u, Pools &pools, const CutSrc &src, int nt, int64_t shift
         for (double v : cms) { sum += v; mx = std::max(mx, v); }
         std::fprintf(stderr, "  merge+refine+collapse+filter in one pass %.1f ms (K=%lld, task sum %.1f max %.1f ms): %lld hits, "
                      "%lld cuts (%lld bits unverified, %lld tasks folded again), merge -> %lld, collapse -> %lld, "
-                     "filter -> %lld; materialise %.1f ms\n",
+                     "filter -> %lld; survivors gathered in %.1f ms\n",
                      d(t0, t1), (long long)K, sum, mx, (long long)n, (long long)n_cuts.load(), (long long)n_unverified.load(),
                      (long long)redone, (long long)n_folded.load(), (long long)n_collapsed.load(), (long long)cnt[(size_t)KS],
                      d(t1, t2));
     }
     if (ms) {
-        ms[2] += d(t0, t1);
-        ms[3] += d(t1, t2);
+        ms[2] += d(t0, t2);
     }
 }
 
+// a fold unit's final records: the fold's survivors in (start, end) order, the
+// arenas their Extras and strings live in, and the frame they are in
+struct UnitRes {
+    ItemVec items;
+    std::unique_ptr<Pools> pools;
+    int64_t shift = 0;       // added to every position (the unit's common trim offset)
+    bool restored = false;   // positions are full-sequence ones already
+    int32_t unit = 0, contigs = 0;
+};
+
 void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vector<HitVec> &raw,
-                  std::vector<ScreenedVec> &shits, RecVec &out, double *ms, int nt) {
+                  std::vector<ScreenedVec> &shits, UnitRes &res, double *ms, int nt) {
     using clk = std::chrono::steady_clock;
     auto t0 = clk::now();
     UnitCtx u{&job, job.params.min_copies};
-    Pools pools(std::max(1, nt));
+    res.pools = std::make_unique<Pools>(std::max(1, nt));
+    Pools &pools = *res.pools;
+    ItemVec &out = res.items;
     // Every unit ends in fold_cuts, the fold to the filter in one pass.  Cut
     // bits are used (BWTMI_FOLD_CUTS, default 1) where screen_reach bounds the
     // records: one contig, strict hits only.  Anything else is one segment.
@@ -1653,6 +1638,9 @@ void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vecto
     bool one_offset = true;
     for (int32_t c : chroms) one_offset = one_offset && job.contigs[(size_t)c].trim_left == job.contigs[(size_t)chroms[0]].trim_left;
     const int64_t shift = one_offset && !chroms.empty() ? job.contigs[(size_t)chroms[0]].trim_left : 0;
+    res.shift = shift;
+    res.restored = !one_offset;   // fold_cuts restores such a unit's one segment before the collapse
+    res.contigs = (int32_t)chroms.size();
     auto d = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     // one device-screened contig without Tier 3 records (the usual unit): the
     // tasks of the pass read its compact hits, which never enter a shared array
@@ -1751,14 +1739,185 @@ void process_unit(const Job &job, const std::vector<int32_t> &chroms, std::vecto
     }
 }
 
+// The units' survivors as the job keeps them (common.h Survivors).  view() and
+// materialize() state the same record: strict fields per bwt.py:1972-1993,
+// recomputed ones from their Extra.
+struct SurvivorSet final : Survivors {
+    const Job *job = nullptr;
+    std::vector<UnitRes> us;   // units with records, in unit order
+    size_t total = 0;
+    size_t size() const override { return total; }
+    size_t units() const override { return us.size(); }
+    int32_t unit_id(size_t k) const override { return us[k].unit; }
+    int32_t unit_chrom(size_t k) const override { return us[k].items[0].chrom; }
+    size_t unit_size(size_t k) const override { return us[k].items.size(); }
+    void span(size_t k, size_t i, int64_t &start, int64_t &end, int32_t &mlen) const override {
+        const Item &it = us[k].items[i];
+        start = it.start + us[k].shift;
+        end = it.end + us[k].shift;
+        mlen = it.mlen;   // every Item's mlen is its motif's length (strict: the primitive unit; recomputed: its Extra's motif)
+    }
+    RecRef view(size_t k, size_t i) const override {
+        const UnitRes &U = us[k];
+        const Item &it = U.items[i];
+        const Contig &c = job->contigs[(size_t)it.chrom];
+        RecRef v;
+        v.chrom = it.chrom;
+        v.tier = tier_of(it);
+        v.start = it.start + U.shift;
+        v.end = it.end + U.shift;
+        if (it.xp) {
+            const Extra &x = *it.x();
+            v.motif = x.motif.data();
+            v.mlen = (int32_t)x.motif.size();
+            v.copies = x.copies;
+            v.confidence = x.confidence;
+            v.mismatch_rate = x.mm;
+            v.max_mm = x.max_mm;
+            v.n_eval = x.n_eval;
+            v.strand = x.strand;
+            v.pmatch = x.pmatch;
+            v.pindel = x.pindel;
+            v.score = x.score;
+            v.var = x.variations.data();
+            v.vlen = (int32_t)x.variations.size();
+            v.stats_none = x.stats_none;
+        } else {
+            v.motif = c.trimmed() + (it.start - (U.restored ? c.trim_left : 0));
+            v.mlen = it.mlen;
+            const int64_t count = strict_copies(it);
+            v.copies = (double)count;
+            v.confidence = 0.95;
+            v.mismatch_rate = 0.0;
+            v.max_mm = 0;
+            v.n_eval = count;
+            v.strand = '+';
+            v.pmatch = (1.0 - 0.0) * 100.0;
+            v.pindel = 0.0;
+            v.score = trf_score(it.end - it.start, 0.0);
+        }
+        // actual_sequence = full_sequence[start:end] after restore (bwt.py:3323-3325)
+        if (!c.full.empty()) {
+            const int64_t L = (int64_t)c.full.size();
+            const int64_t a = std::min(v.start, L), b = std::max(a, std::min(v.end, L));
+            v.act = c.full.data() + a;
+            v.act_len = b - a;
+        }
+        return v;
+    }
+    // Every slot is constructed whatever throws: a task whose materialize
+    // throws constructs the rest of its slots before it reports, and the tasks
+    // after it only construct theirs, so the vector's destructor never meets a
+    // raw slot.
+    void materialize(RecVec &out, int nt) const override {
+        struct Task { size_t k, a, b, o; };
+        std::vector<Task> tasks;
+        size_t o = 0;
+        for (size_t k = 0; k < us.size(); ++k)
+            for (size_t a = 0, n = us[k].items.size(); a < n; a += 4096) {
+                tasks.push_back({k, a, std::min(n, a + 4096), o});
+                o += std::min(n, a + 4096) - a;
+            }
+        {
+            DeferConstruct raw;   // constructed below, in parallel
+            out.resize(total);
+        }
+        static_assert(std::is_nothrow_default_constructible<Rec>::value, "Rec() must not throw");
+        // test hook: BWTMI_FAIL_MATERIALISE != 0 throws inside the last task
+        const bool inject = knob(KN_FAIL_MATERIALISE) != 0;
+        std::atomic<bool> failed{false};
+        std::exception_ptr err;
+        std::mutex err_mu;
+        parallel_items((int64_t)tasks.size(), nt, [&](int64_t t, int) {
+            const Task &T = tasks[(size_t)t];
+            const UnitRes &U = us[T.k];
+            UnitCtx u{job, job->params.min_copies};
+            u.restored = U.restored;
+            size_t q = T.o;   // slots [T.o, q) are constructed
+            const size_t q1 = T.o + (T.b - T.a);
+            if (!failed.load(std::memory_order_relaxed)) {
+                try {
+                    for (size_t j = T.a; j < T.b; ++j) {
+                        if (j + 8 < T.b && U.items[j + 8].xp) __builtin_prefetch(U.items[j + 8].x());
+                        ::new ((void *)&out[q]) Rec();
+                        ++q;
+                        bwtmi::materialize(u, U.items[j], U.shift, out[q - 1]);
+                    }
+                    if (inject && (size_t)t + 1 == tasks.size()) fail(BWTMI_E_STATE, "injected failure building the records");
+                } catch (...) {
+                    failed.store(true, std::memory_order_relaxed);
+                    std::lock_guard<std::mutex> lk(err_mu);
+                    if (!err) err = std::current_exception();
+                }
+            }
+            for (; q < q1; ++q) ::new ((void *)&out[q]) Rec();
+        });
+        if (err) std::rethrow_exception(err);
+    }
+};
+
 }  // namespace
+
+// The records are built from the survivors by the first reader that asks for
+// them; two threads may ask at once.  A failure leaves them pending.
+RecVec &Job::recs() {
+    std::lock_guard<std::mutex> lk(recs_mu);
+    if (recs_pending) {
+        RecVec built;
+        surv->materialize(built, host_threads(params));
+        final_recs.swap(built);
+        recs_pending = false;
+    }
+    return final_recs;
+}
+
+RecVec &Job::recs_own() {
+    RecVec &r = recs();
+    std::shared_ptr<Survivors> old;
+    {
+        std::lock_guard<std::mutex> lk(recs_mu);
+        old.swap(surv);
+    }
+    if (old) defer([old]() mutable { old.reset(); });
+    return r;
+}
+
+size_t Job::count() const {
+    std::lock_guard<std::mutex> lk(recs_mu);
+    return recs_pending ? surv->size() : final_recs.size();
+}
+
+std::shared_ptr<Survivors> Job::survivors() const {
+    std::lock_guard<std::mutex> lk(recs_mu);
+    return surv;
+}
+
+void Job::keep_survivors(std::shared_ptr<Survivors> s) {
+    std::lock_guard<std::mutex> lk(recs_mu);
+    surv = std::move(s);
+    recs_pending = true;
+}
+
+void Job::drop_results() {
+    std::lock_guard<std::mutex> lk(recs_mu);
+    recs_pending = false;
+    // released on the background reaper thread, behind the next step's device phase
+    auto old_s = std::make_shared<std::shared_ptr<Survivors>>(std::move(surv));
+    surv = nullptr;
+    auto old_r = std::make_shared<RecVec>();
+    old_r->swap(final_recs);
+    defer([old_s, old_r] {
+        old_s->reset();
+        RecVec().swap(*old_r);
+    });
+}
 
 void postprocess(Job &job) {
     job.assign_units();
     std::vector<std::vector<int32_t>> units((size_t)job.nunits);
     for (size_t c = 0; c < job.contigs.size(); ++c) units[(size_t)job.contigs[c].unit].push_back((int32_t)c);
     if (job.hits.size() < job.contigs.size()) job.hits.resize(job.contigs.size());
-    std::vector<RecVec> res((size_t)job.nunits);
+    std::vector<UnitRes> res((size_t)job.nunits);
     std::vector<double> ms((size_t)job.nunits * 4, 0.0);
     const int T = host_threads(job.params);
     // many small units: one thread per unit; few large units: all threads inside each
@@ -1815,43 +1974,44 @@ void postprocess(Job &job) {
                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count());
         }
     }
-    job.final_recs.clear();
-    size_t tot = 0, nonempty = 0, last = 0;
-    for (size_t k = 0; k < res.size(); ++k)
-        if (!res[k].empty()) {
-            tot += res[k].size();
-            ++nonempty;
-            last = k;
-        }
-    if (nonempty <= 1) {   // one unit with records (one contig, or this rank's only one): no copy
-        if (nonempty) job.final_recs.swap(res[last]);
-    } else {   // the units' records moved into place in parallel
-        std::vector<size_t> at(res.size() + 1, 0);
-        for (size_t k = 0; k < res.size(); ++k) at[k + 1] = at[k] + res[k].size();
-        {
-            DeferConstruct raw;   // move-constructed below, in parallel
-            job.final_recs.resize(tot);
-        }
-        static_assert(std::is_nothrow_move_constructible<Rec>::value, "the parallel moves must not throw");
-        run_tasks((int64_t)res.size(), T, [&](int64_t k) {
-            Rec *d = job.final_recs.data() + at[(size_t)k];
-            for (Rec &r : res[(size_t)k]) ::new ((void *)d++) Rec(std::move(r));
-        });
+    // The units with records are kept as they are when each is one contig;
+    // otherwise (a unit whose rows interleave several chromosomes) the records
+    // are built now.
+    job.drop_results();
+    auto set = std::make_shared<SurvivorSet>();
+    set->job = &job;
+    bool one_contig_units = true;
+    for (int32_t k = 0; k < job.nunits; ++k) {
+        UnitRes &R = res[(size_t)k];
+        if (R.items.empty()) continue;
+        R.unit = k;
+        one_contig_units = one_contig_units && R.contigs == 1;
+        set->total += R.items.size();
+        set->us.push_back(std::move(R));
     }
-    // the units' emptied vectors are released behind the next stage
-    {
-        auto old = std::make_shared<std::vector<RecVec>>(std::move(res));
+    {   // what is left of the units (empty arenas) is released behind the next stage
+        auto old = std::make_shared<std::vector<UnitRes>>(std::move(res));
         defer([old] { old->clear(); });
+    }
+    double built_ms = 0;
+    if (one_contig_units) {
+        job.keep_survivors(set);
+    } else {
+        const auto b0 = std::chrono::steady_clock::now();
+        set->materialize(job.final_recs, T);
+        built_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b0).count();
+        defer([set]() mutable { set.reset(); });
     }
     for (int s = 0; s < 4; ++s) {
         job.stage_ms[2 + s] = 0;
         for (int32_t k = 0; k < job.nunits; ++k) job.stage_ms[2 + s] += ms[(size_t)k * 4 + s];
     }
+    job.stage_ms[5] = built_ms;   // records built inside this call (none when the survivors are kept)
     if (stats_on(2))
         std::fprintf(stderr, "[bwtmi] recomputes=%lld (%.1f ms thread-summed; %lld reused walks) merges=%lld canons=%lld "
                      "final=%zu\n", (long long)g_recomputes.exchange(0), g_recompute_ns.exchange(0) / 1e6,
                      (long long)g_walk_reuse.exchange(0), (long long)g_merges.exchange(0),
-                     (long long)g_canons.exchange(0), job.final_recs.size());
+                     (long long)g_canons.exchange(0), job.count());
     if (stats_on(2))
         std::fprintf(stderr, "[bwtmi] merge tests past the gap test=%lld, same canonical=%lld\n",
                      (long long)g_tests.exchange(0), (long long)g_same.exchange(0));

@@ -4,7 +4,9 @@
 // Python's "{x:.Nf}" and C's "%.Nf" both print the exact binary value rounded
 // half-to-even, so numeric columns are byte-identical.
 #include <algorithm>
+#include <atomic>
 #include <map>
+#include <mutex>
 #include <thread>
 #include <optional>
 #include <chrono>
@@ -30,42 +32,68 @@ struct View {
     bool empty() const { return n <= 0; }
 };
 
-View act_of(const Job &job, const Rec &r) {
-    View v;
-    if (r.act_kind == ACT_NONE) return v;
-    const Contig &c = job.contigs[(size_t)r.chrom];
-    v.p = (r.act_kind == ACT_FULL ? c.full.data() : c.trimmed()) + r.act_off;
-    v.n = r.act_len;
+// the view of a final record (valid while the record and its contig's text are)
+RecRef ref_of(const Job &job, const Rec &r) {
+    RecRef v;
+    v.start = r.start;
+    v.end = r.end;
+    v.copies = r.copies;
+    v.pmatch = r.pmatch;
+    v.pindel = r.pindel;
+    v.mismatch_rate = r.mismatch_rate;
+    v.confidence = r.confidence;
+    v.n_eval = r.n_eval;
+    v.max_mm = r.max_mm;
+    v.score = r.score;
+    v.motif = r.motif.data();
+    v.mlen = (int32_t)r.motif.size();
+    v.var = r.variations.data();
+    v.vlen = (int32_t)r.variations.size();
+    if (r.act_kind != ACT_NONE) {
+        const Contig &c = job.contigs[(size_t)r.chrom];
+        v.act = (r.act_kind == ACT_FULL ? c.full.data() : c.trimmed()) + r.act_off;
+        v.act_len = r.act_len;
+    }
+    v.chrom = r.chrom;
+    v.tier = r.tier;
+    v.strand = r.strand;
+    v.kmer_stats = r.kmer_stats;
+    v.stats_none = r.stats_none;
     return v;
 }
 
-Rec kmer_piece(int32_t chrom, int64_t start, int64_t end, const std::string &motif, int64_t copies,
-               int32_t tier, int8_t kind, int64_t off, int64_t len) {
-    Rec r;
-    r.chrom = chrom;
-    r.start = start;
-    r.end = end;
-    r.length = end - start;
-    r.motif = motif;
-    r.copies = (double)copies;
-    r.tier = tier;
-    r.confidence = 1.0;
-    r.mismatch_rate = 0.0;
-    r.max_mm = 0;
-    r.n_eval = copies;
-    r.strand = '+';
-    r.pmatch = 100.0;
-    r.pindel = 0.0;
-    r.score = 100;
-    r.kmer_stats = true;
-    r.act_kind = kind;
-    r.act_off = off;
-    r.act_len = len;
-    return r;
+// a compound-stage piece (bwt.py:3980-3987, 4074-4091): its motif and its
+// actual sequence are bytes of the contig
+RecRef piece_ref(int32_t chrom, int64_t start, int64_t end, const char *motif, int32_t mlen, int64_t copies,
+                 int32_t tier, const char *act, int64_t act_len) {
+    RecRef v;
+    v.start = start;
+    v.end = end;
+    v.copies = (double)copies;
+    v.pmatch = 100.0;
+    v.pindel = 0.0;
+    v.mismatch_rate = 0.0;
+    v.confidence = 1.0;
+    v.n_eval = copies;
+    v.max_mm = 0;
+    v.score = 100;
+    v.motif = motif;
+    v.mlen = mlen;
+    v.act = act;
+    v.act_len = act_len;
+    v.chrom = chrom;
+    v.tier = tier;
+    v.strand = '+';
+    v.kmer_stats = true;
+    return v;
+}
+
+inline bool same_motif(const RecRef &a, const RecRef &b) {
+    return a.mlen == b.mlen && std::memcmp(a.motif, b.motif, (size_t)a.mlen) == 0;
 }
 
 // _simple_kmer_scan(chrom, start, end, k=3, use_full_seq=True)
-void kmer_scan(const Job &job, int32_t chrom, int64_t start, int64_t end, RecVec &out) {
+void kmer_scan(const Job &job, int32_t chrom, int64_t start, int64_t end, std::vector<RecRef> &out) {
     const Seq &seq = job.contigs[(size_t)chrom].full;
     const int64_t L = (int64_t)seq.size();
     const int64_t k = 3;
@@ -80,8 +108,7 @@ void kmer_scan(const Job &job, int32_t chrom, int64_t start, int64_t end, RecVec
             j += k;
         }
         if (c >= 5) {
-            out.push_back(kmer_piece(chrom, start + i, start + j, std::string(reg + i, (size_t)k), c, 1,
-                                     ACT_FULL, start + i, j - i));
+            out.push_back(piece_ref(chrom, start + i, start + j, reg + i, (int32_t)k, c, 1, reg + i, j - i));
             i = j;
         } else {
             ++i;
@@ -89,313 +116,198 @@ void kmer_scan(const Job &job, int32_t chrom, int64_t start, int64_t end, RecVec
     }
 }
 
-// one output row of the STRfinder writer: a final record or a compound piece,
-// with its compound partner (bwt.py:4126-4130)
-struct Row {
-    const Rec *r;
-    const Rec *partner;   // nullptr unless is_compound
-    int64_t start, end;   // r's, kept inline so ordering the rows reads no record
-    int32_t unit;
+// span of a > 10 bp motif, with the prefix maximum of the ends up to it
+struct Long { int64_t s, e, pe; };
+
+// The records one walk of _detect_compound_repeats (bwt.py:3995-4139) runs
+// over: one chromosome's final records in start order with the k-mer pieces
+// merged in behind the records of equal start (the reference appends them and
+// sorts stably by start, bwt.py:4011-4026).  The merged list is never built:
+// index m is piece k when ppos[k] == m, else final record m - (pieces before m).
+struct Merged {
+    const Rec *main = nullptr;          // n_main consecutive records, or
+    const Rec *const *list = nullptr;   // n_main pointers, or
+    const Survivors *sv = nullptr;      // the fold's survivors of unit su
+    size_t su = 0;
+    size_t n_main = 0;
+    const RecRef *pieces = nullptr;
+    const size_t *ppos = nullptr;
+    size_t np = 0;
+    const Long *longs = nullptr;
+    size_t nl = 0;
+    int32_t chrom = 0;
+    size_t size() const { return n_main + np; }
+    const Rec &rec(size_t k) const { return list ? *list[k] : main[k]; }
+    // m is a piece: its index (true); else the final record's index
+    bool piece_at(size_t m, size_t &k) const {
+        k = m;
+        if (!np) return false;
+        const size_t q = (size_t)(std::lower_bound(ppos, ppos + np, m) - ppos);
+        if (q < np && ppos[q] == m) {
+            k = q;
+            return true;
+        }
+        k = m - q;
+        return false;
+    }
+    int64_t main_start(size_t k) const {
+        if (!sv) return rec(k).start;
+        int64_t s, e;
+        int32_t ml;
+        sv->span(su, k, s, e, ml);
+        return s;
+    }
+    // final records with a start <= s
+    size_t mains_upto(int64_t s) const {
+        size_t lo = 0, hi = n_main;
+        while (lo < hi) {
+            const size_t mid = lo + (hi - lo) / 2;
+            if (s < main_start(mid)) hi = mid;
+            else lo = mid + 1;
+        }
+        return lo;
+    }
+    RecRef view(const Job &job, size_t m) const {
+        size_t k;
+        return piece_at(m, k) ? pieces[k] : sv ? sv->view(su, k) : ref_of(job, rec(k));
+    }
+    int64_t start_at(size_t m) const {
+        size_t k;
+        return piece_at(m, k) ? pieces[k].start : main_start(k);
+    }
 };
 
-inline Row row_of(const Job &job, const Rec *r, const Rec *partner) {
-    return Row{r, partner, r->start, r->end, job.contigs[(size_t)r->chrom].unit};
-}
+// one row of a walk: indices into the walk's views (>= 0) or its split pieces (~index)
+struct WRow { int32_t r, p; };
+constexpr int32_t kNoRec = INT32_MIN;
+// a row ready for the formatter (bwt.py:4126-4130: a record or a compound
+// piece, with its partner)
+struct FRow { const RecRef *r, *p; };
 
-struct Compound {
-    std::deque<Rec> pool;                // k-mer pieces, pointer-stable
-    std::deque<std::deque<Rec>> pools;   // split pieces of the walk chunks (a moved deque keeps its
-                                         // elements in place; the outer deque never moves its deques)
-    std::vector<Row> rows;
-};
-
-// rows emitted by a walk over some indices, with the index each was emitted from
+// A walk from merged index m0.  Its only state is the index; a step consumes 1
+// or 2 records, or more after splits, and emits rows.  The views are built as
+// the walk reaches them; rows hold indices and are resolved to pointers once
+// the walk is over (the vectors may grow until then).
 struct Walk {
-    std::vector<Row> rows;
-    std::vector<size_t> at;
-    std::deque<Rec> pool;
-    size_t next = 0;
-    void emit(Row r, size_t i0) {
-        rows.push_back(r);
-        at.push_back(i0);
+    const Job &job;
+    const Merged &M;
+    const size_t m0;
+    std::vector<RecRef> vw, spl;
+    std::vector<WRow> rows;
+    std::vector<uint32_t> at;   // rows[k] was emitted by the step from m0 + at[k]
+    std::vector<int32_t> run_from;
+    Walk(const Job &j, const Merged &m, size_t from, size_t expect = 0) : job(j), M(m), m0(from) {
+        vw.reserve(expect + 8);
+        rows.reserve(expect + 8);
+        at.reserve(expect + 8);
+    }
+    void reach(size_t m) {   // views up to m exist (earlier references may move)
+        while (vw.size() <= m - m0) vw.push_back(M.view(job, m0 + vw.size()));
+    }
+    const RecRef *ref(int32_t x) const { return x == kNoRec ? nullptr : x >= 0 ? &vw[(size_t)x] : &spl[(size_t)~x]; }
+    void emit(int32_t r, int32_t p, size_t i0) {
+        rows.push_back({r, p});
+        at.push_back((uint32_t)(i0 - m0));
+    }
+    void plain(size_t i) {   // the formats without compounds: every record is a row
+        reach(i);
+        emit((int32_t)(i - m0), kNoRec, i);
+    }
+    size_t step(size_t i) {
+        const size_t i0 = i, N = M.size();
+        reach(std::min(i + 1, N - 1));
+        const RecRef cur = vw[i - m0];   // (a copy: the views may move below)
+        const Contig &ctg = job.contigs[(size_t)M.chrom];
+        const int64_t TL = ctg.trimmed_len();
+        if (cur.mlen == 3 && cur.copies >= 10 && TL > 0) {
+            // repeat_seq = sequences[chrom][cur.start:cur.end] (trimmed sequence, restored
+            // coordinates -- bwt.py:4045-4047)
+            const char *tseq = ctg.trimmed();
+            const int64_t a = std::min(std::max<int64_t>(cur.start, 0), TL);
+            const int64_t b = std::max(a, std::min(std::max<int64_t>(cur.end, 0), TL));
+            const char *rsq = tseq + a;
+            const int64_t rl = b - a;
+            const int64_t k = 3;
+            // Every split point sp (k <= sp < rl - k, a multiple of k) sees whole
+            // copies only: l1 = l2 = k, c1 = the leading copies equal to copy 0,
+            // capped at sp / k, and c2 = the run of copies equal to copy sp/k
+            // (exact equality chains), so both come from one pass over the
+            // copies instead of a rescan per split point (O(copies), not O(copies^2))
+            const int64_t nq = rl / k;   // whole copies
+            int64_t lead = 0;
+            if (rl - k > k) {
+                while (lead < nq && std::memcmp(rsq + lead * k, rsq, (size_t)k) == 0) ++lead;
+                run_from.assign((size_t)nq + 1, 0);
+                for (int64_t q = nq - 1; q >= 0; --q)
+                    run_from[(size_t)q] = 1 + (q + 1 < nq && std::memcmp(rsq + q * k, rsq + (q + 1) * k, (size_t)k) == 0
+                                                   ? run_from[(size_t)q + 1] : 0);
+            }
+            for (int64_t sp = k; sp < rl - k; sp += k) {
+                const int64_t l1 = k, l2 = k;
+                if (std::memcmp(rsq, rsq + sp, (size_t)k) == 0) continue;
+                const int64_t c1 = std::min<int64_t>(lead, sp / k);
+                const int64_t c2 = run_from[(size_t)(sp / k)];
+                if (c1 >= 5 && c2 >= 5 && (double)(c1 * l1 + c2 * l2) >= (double)rl * 0.9) {
+                    const int64_t e1 = cur.start + c1 * l1;
+                    // actual = repeat_seq[:c1*l1], repeat_seq[c1*l1 : c1*l1 + c2*l2]
+                    const int64_t x1 = std::min(c1 * l1, rl);
+                    const int64_t y0 = std::min(c1 * l1, rl), y1 = std::max(y0, std::min(c1 * l1 + c2 * l2, rl));
+                    spl.push_back(piece_ref(M.chrom, cur.start, e1, rsq, (int32_t)l1, c1, cur.tier, tseq + a, x1));
+                    spl.push_back(piece_ref(M.chrom, e1, e1 + c2 * l2, rsq + sp, (int32_t)l2, c2, cur.tier,
+                                            tseq + a + y0, y1 - y0));
+                    emit(~(int32_t)(spl.size() - 2), ~(int32_t)(spl.size() - 1), i0);
+                    ++i;   // the reference advances i inside the split loop (bwt.py:4083)
+                }
+            }
+        }
+        if (i + 1 < N) {
+            reach(i + 1);
+            const RecRef &nx = vw[i + 1 - m0];
+            const int64_t gap = nx.start - cur.end;
+            if (gap <= 5 && cur.mlen <= 4 && nx.mlen <= 4 && !same_motif(cur, nx) && cur.copies >= 5 && nx.copies >= 5) {
+                const int64_t cs = cur.start, ce = nx.end;
+                // any(long overlaps >= 80 %): a long with s >= ce or e <= cs has
+                // ov = 0, so only those before the first s >= ce whose prefix
+                // max end still exceeds cs can qualify
+                bool covered = false;
+                size_t k = (size_t)(std::lower_bound(M.longs, M.longs + M.nl, ce,
+                                                     [](const Long &l, int64_t x) { return l.s < x; }) - M.longs);
+                while (k > 0 && !covered) {
+                    const Long &lm = M.longs[--k];
+                    if (lm.pe <= cs) break;
+                    const int64_t ov = std::max<int64_t>(0, std::min(ce, lm.e) - std::max(cs, lm.s));
+                    if ((double)ov / (double)(ce - cs) >= 0.8) covered = true;
+                }
+                if (!covered) {
+                    emit((int32_t)(i0 - m0), (int32_t)(i + 1 - m0), i0);
+                    return i + 2;
+                }
+            }
+        }
+        emit((int32_t)(i0 - m0), kNoRec, i0);
+        return i + 1;
+    }
+    void resolve(std::vector<FRow> &out) const {
+        for (const WRow &w : rows) out.push_back({ref(w.r), ref(w.p)});
     }
 };
 
-// _detect_compound_repeats (bwt.py:3995-4139) over the final records; works on
-// pointers, so the final records are never copied
-void detect_compounds(const Job &job, const RecVec &recs, Compound &out, int nt) {
-    auto T0 = std::chrono::steady_clock::now();
-    // one pass over the records, in parallel chunks: chromosome of each and the
-    // _simple_kmer_scan pieces after every 3-mer record (kept in record order)
-    const size_t NR = recs.size();
-    const int CK = NR > 8192 ? 4 * std::max(1, nt) : 1;
-    struct Chunk {
-        int32_t first = -1;
-        bool mixed = false;
-        std::vector<size_t> bounds;                   // q in the chunk with recs[q].chrom != recs[q - 1].chrom
-        std::vector<std::pair<size_t, Rec>> pieces;   // (record index, piece)
-    };
-    std::vector<Chunk> ck((size_t)CK);
-    run_tasks(CK, nt, [&](int64_t t) {
-        Chunk &C = ck[(size_t)t];
-        RecVec kr;
-        for (size_t q = NR * (size_t)t / (size_t)CK; q < NR * (size_t)(t + 1) / (size_t)CK; ++q) {
-            const Rec &r = recs[q];
-            if (C.first < 0) C.first = r.chrom;
-            else if (r.chrom != C.first) C.mixed = true;
-            if (q > 0 && r.chrom != recs[q - 1].chrom) C.bounds.push_back(q);
-            if (r.motif.size() != 3) continue;
-            const Seq &full = job.contigs[(size_t)r.chrom].full;
-            if (full.empty()) continue;
-            const int64_t a = r.end, b = std::min<int64_t>((int64_t)full.size(), r.end + 50);
-            if (a >= b) continue;
-            kr.clear();
-            kmer_scan(job, r.chrom, a, b, kr);
-            for (auto &x : kr)
-                if (x.motif != r.motif) C.pieces.emplace_back(q, std::move(x));
+// rows in start order: the runs of equal start go by end, stably -- which makes
+// them sorted(key=(start, end)) (bwt.py:4150; runs are short)
+void order_equal_starts(std::vector<FRow> &rows) {
+    for (size_t i = 0; i < rows.size();) {
+        size_t j = i + 1;
+        while (j < rows.size() && rows[j].r->start == rows[i].r->start) ++j;
+        for (size_t a = i + 1; a < j; ++a) {
+            const FRow x = rows[a];
+            size_t q = a;
+            while (q > i && rows[q - 1].r->end > x.r->end) {
+                rows[q] = rows[q - 1];
+                --q;
+            }
+            rows[q] = x;
         }
-    });
-    bool single = true;
-    for (auto &C : ck) single = single && !C.mixed && (C.first < 0 || C.first == ck[0].first);
-    std::vector<int32_t> chrom_order;
-    std::vector<std::vector<const Rec *>> by(job.contigs.size());
-    if (single && NR > 0) {   // one chromosome: its list is every record, in order
-        chrom_order.push_back(recs[0].chrom);
-        auto &lst = by[(size_t)recs[0].chrom];
-        lst.resize(NR);
-        run_tasks(CK, nt, [&](int64_t t) {
-            for (size_t q = NR * (size_t)t / (size_t)CK; q < NR * (size_t)(t + 1) / (size_t)CK; ++q) lst[q] = &recs[q];
-        });
-    } else if (NR > 0) {
-        // the usual multi-contig list: each chromosome's records are one contiguous
-        // run (the fold units are concatenated), so every list is a range, filled in
-        // parallel; otherwise one serial pass
-        std::vector<size_t> runs{0};   // start of each run of equal chromosome
-        for (auto &C : ck) runs.insert(runs.end(), C.bounds.begin(), C.bounds.end());
-        runs.push_back(NR);
-        bool contiguous = true;
-        {
-            std::vector<uint8_t> seen(job.contigs.size(), 0);
-            for (size_t k = 0; k + 1 < runs.size() && contiguous; ++k) {
-                const size_t ch = (size_t)recs[runs[k]].chrom;
-                contiguous = !seen[ch];
-                seen[ch] = 1;
-            }
-        }
-        if (contiguous) {
-            for (size_t k = 0; k + 1 < runs.size(); ++k) {
-                const int32_t ch = recs[runs[k]].chrom;
-                chrom_order.push_back(ch);
-                by[(size_t)ch].resize(runs[k + 1] - runs[k]);
-            }
-            run_tasks(CK, nt, [&](int64_t t) {
-                const size_t a = NR * (size_t)t / (size_t)CK, b = NR * (size_t)(t + 1) / (size_t)CK;
-                size_t k = (size_t)(std::upper_bound(runs.begin(), runs.end(), a) - runs.begin()) - 1;
-                for (size_t q = a; q < b; ++q) {
-                    while (q >= runs[k + 1]) ++k;
-                    by[(size_t)recs[q].chrom][q - runs[k]] = &recs[q];
-                }
-            });
-        } else {
-            for (const Rec &r : recs) {
-                if (by[(size_t)r.chrom].empty()) chrom_order.push_back(r.chrom);
-                by[(size_t)r.chrom].push_back(&r);
-            }
-        }
-    }
-    auto T1 = std::chrono::steady_clock::now();
-    std::vector<size_t> n_main(job.contigs.size(), 0);
-    for (int32_t ch : chrom_order) n_main[(size_t)ch] = by[(size_t)ch].size();
-    // pieces go behind their chromosome's records, in record order (bwt.py:4011-4024)
-    for (auto &C : ck)
-        for (auto &pc : C.pieces) {
-            out.pool.push_back(std::move(pc.second));
-            by[(size_t)recs[pc.first].chrom].push_back(&out.pool.back());
-        }
-    auto T2 = std::chrono::steady_clock::now();
-    double tsort = 0;
-    for (int32_t ch : chrom_order) {
-        auto S0 = std::chrono::steady_clock::now();
-        std::vector<const Rec *> &rs = by[(size_t)ch];
-        // stable sort by start: the final records arrive sorted, only the
-        // k-mer pieces appended behind them need ordering and a stable merge
-        auto by_start = [](const Rec *a, const Rec *b) { return a->start < b->start; };
-        const size_t nmain = n_main[(size_t)ch];
-        std::vector<uint8_t> chunk_sorted((size_t)CK, 1);
-        run_tasks(CK, nt, [&](int64_t t) {   // chunk t checks the pairs ending in it
-            const size_t a = std::max<size_t>(1, nmain * (size_t)t / (size_t)CK), b = nmain * (size_t)(t + 1) / (size_t)CK;
-            for (size_t k = a; k < b; ++k)
-                if (rs[k]->start < rs[k - 1]->start) { chunk_sorted[(size_t)t] = 0; return; }
-        });
-        bool main_sorted = true;
-        for (auto v : chunk_sorted) main_sorted = main_sorted && v;
-        if (main_sorted && rs.size() > nmain) {
-            // few k-mer pieces into a long sorted list: each piece goes behind the
-            // main records with an equal start (a stable merge), and the main
-            // list is copied in parallel segments between the insertion points
-            std::stable_sort(rs.begin() + (std::ptrdiff_t)nmain, rs.end(), by_start);
-            const size_t np = rs.size() - nmain;
-            std::vector<size_t> at(np);
-            for (size_t q = 0; q < np; ++q)
-                at[q] = (size_t)(std::upper_bound(rs.begin(), rs.begin() + (std::ptrdiff_t)nmain, rs[nmain + q], by_start) -
-                                 rs.begin());
-            std::vector<const Rec *> merged(rs.size());
-            run_tasks((int64_t)np + 1, nt, [&](int64_t q) {   // segment q: main [at[q-1], at[q]) then piece q
-                const size_t a0 = q ? at[(size_t)q - 1] : 0, a1 = (size_t)q < np ? at[(size_t)q] : nmain;
-                std::copy(rs.begin() + (std::ptrdiff_t)a0, rs.begin() + (std::ptrdiff_t)a1,
-                          merged.begin() + (std::ptrdiff_t)(a0 + (size_t)q));
-                if ((size_t)q < np) merged[a1 + (size_t)q] = rs[nmain + (size_t)q];
-            });
-            rs.swap(merged);
-        } else if (main_sorted) {
-        } else {
-            std::stable_sort(rs.begin(), rs.end(), by_start);
-        }
-        // spans of the > 10 bp motifs in start order, with the prefix max of
-        // their ends: the "covered" test visits only those that can overlap
-        struct Long { int64_t s, e, pe; };
-        std::vector<std::vector<Long>> lpart((size_t)CK);
-        const size_t NS = rs.size();
-        run_tasks(CK, nt, [&](int64_t t) {
-            for (size_t k = NS * (size_t)t / (size_t)CK; k < NS * (size_t)(t + 1) / (size_t)CK; ++k)
-                if (rs[k]->motif.size() > 10) lpart[(size_t)t].push_back({rs[k]->start, rs[k]->end, 0});
-        });
-        std::vector<Long> longs;
-        for (auto &lp : lpart)
-            for (auto &l : lp) {
-                l.pe = longs.empty() ? l.e : std::max(longs.back().pe, l.e);
-                longs.push_back(l);
-            }
-        tsort += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - S0).count();
-        const Contig &ctg = job.contigs[(size_t)ch];
-        const int64_t TL = ctg.trimmed_len();
-        const char *tseq = ctg.trimmed();
-        // The walk's only state is the index i; a step may consume 1 or 2
-        // records, or more after splits.  Chunks are walked speculatively in
-        // parallel as if the walk arrived at their first index; a serial
-        // repair walks from the true index until it reaches an index the
-        // speculative run also stepped from, after which the two coincide.
-        const size_t N = rs.size();
-        auto step = [&](size_t i, Walk &w) -> size_t {
-            const size_t i0 = i;
-            const Rec *cur = rs[i];
-            if (cur->motif.size() == 3 && cur->copies >= 10 && TL > 0) {
-                // repeat_seq = sequences[chrom][cur.start:cur.end] (trimmed sequence, restored
-                // coordinates -- bwt.py:4045-4047)
-                const int64_t a = std::min(std::max<int64_t>(cur->start, 0), TL);
-                const int64_t b = std::max(a, std::min(std::max<int64_t>(cur->end, 0), TL));
-                const char *rsq = tseq + a;
-                const int64_t rl = b - a;
-                const int64_t k = 3;
-                // Every split point sp (k <= sp < rl - k, a multiple of k) sees whole
-                // copies only: l1 = l2 = k, c1 = the leading copies equal to copy 0,
-                // capped at sp / k, and c2 = the run of copies equal to copy sp/k
-                // (exact equality chains), so both come from one pass over the
-                // copies instead of a rescan per split point (O(copies), not O(copies^2))
-                thread_local std::vector<int32_t> run_from;
-                const int64_t nq = rl / k;   // whole copies
-                int64_t lead = 0;
-                if (rl - k > k) {
-                    while (lead < nq && std::memcmp(rsq + lead * k, rsq, (size_t)k) == 0) ++lead;
-                    run_from.assign((size_t)nq + 1, 0);
-                    for (int64_t q = nq - 1; q >= 0; --q)
-                        run_from[(size_t)q] = 1 + (q + 1 < nq && std::memcmp(rsq + q * k, rsq + (q + 1) * k, (size_t)k) == 0
-                                                       ? run_from[(size_t)q + 1] : 0);
-                }
-                for (int64_t sp = k; sp < rl - k; sp += k) {
-                    const int64_t l1 = k, l2 = k;
-                    if (std::memcmp(rsq, rsq + sp, (size_t)k) == 0) continue;
-                    const int64_t c1 = std::min<int64_t>(lead, sp / k);
-                    const int64_t c2 = run_from[(size_t)(sp / k)];
-                    if (c1 >= 5 && c2 >= 5 && (double)(c1 * l1 + c2 * l2) >= (double)rl * 0.9) {
-                        const int64_t e1 = cur->start + c1 * l1;
-                        // actual = repeat_seq[:c1*l1], repeat_seq[c1*l1 : c1*l1 + c2*l2]
-                        const int64_t x1 = std::min(c1 * l1, rl);
-                        const int64_t y0 = std::min(c1 * l1, rl), y1 = std::max(y0, std::min(c1 * l1 + c2 * l2, rl));
-                        w.pool.push_back(kmer_piece(ch, cur->start, e1, std::string(rsq, (size_t)l1), c1, cur->tier,
-                                                      ACT_TRIMMED, a, x1));
-                        Rec *r1 = &w.pool.back();
-                        w.pool.push_back(kmer_piece(ch, e1, e1 + c2 * l2, std::string(rsq + sp, (size_t)l2), c2,
-                                                      cur->tier, ACT_TRIMMED, a + y0, y1 - y0));
-                        r1->is_compound = true;
-                        w.emit(row_of(job, r1, &w.pool.back()), i0);
-                        ++i;   // the reference advances i inside the split loop (bwt.py:4083)
-                    }
-                }
-            }
-            if (i + 1 < N) {
-                const Rec *nx = rs[i + 1];
-                const int64_t gap = nx->start - cur->end;
-                if (gap <= 5 && cur->motif.size() <= 4 && nx->motif.size() <= 4 && cur->motif != nx->motif &&
-                    cur->copies >= 5 && nx->copies >= 5) {
-                    const int64_t cs = cur->start, ce = nx->end;
-                    // any(long overlaps >= 80 %): a long with s >= ce or e <= cs has
-                    // ov = 0, so only those before the first s >= ce whose prefix
-                    // max end still exceeds cs can qualify
-                    bool covered = false;
-                    size_t k = (size_t)(std::lower_bound(longs.begin(), longs.end(), ce,
-                                                         [](const Long &l, int64_t x) { return l.s < x; }) -
-                                        longs.begin());
-                    while (k > 0 && !covered) {
-                        const Long &lm = longs[--k];
-                        if (lm.pe <= cs) break;
-                        const int64_t ov = std::max<int64_t>(0, std::min(ce, lm.e) - std::max(cs, lm.s));
-                        if ((double)ov / (double)(ce - cs) >= 0.8) covered = true;
-                    }
-                    if (!covered) {
-                        w.emit(row_of(job, cur, nx), i0);
-                        return i + 2;
-                    }
-                }
-            }
-            w.emit(row_of(job, cur, nullptr), i0);
-            return i + 1;
-        };
-        const int K = N > 8192 ? 4 * std::max(1, nt) : 1;
-        std::vector<size_t> cut((size_t)K + 1);
-        for (int k = 0; k <= K; ++k) cut[(size_t)k] = N * (size_t)k / (size_t)K;
-        std::vector<uint8_t> from(N, 0);   // from[i]: the speculative run of i's chunk stepped from i
-        std::vector<Walk> W((size_t)K);
-        run_tasks(K, nt, [&](int64_t k) {
-            size_t i = cut[(size_t)k];
-            Walk &w = W[(size_t)k];
-            w.rows.reserve(cut[(size_t)k + 1] - i + 16);
-            w.at.reserve(cut[(size_t)k + 1] - i + 16);
-            while (i < cut[(size_t)k + 1]) {
-                from[i] = 1;
-                i = step(i, w);
-            }
-            w.next = i;
-        });
-        // the serial repair only decides which rows are taken; they are
-        // copied into place afterwards, in parallel
-        std::vector<Walk> reps((size_t)K);
-        std::vector<std::pair<const Row *, size_t>> seg;
-        size_t ti = 0;
-        for (int k = 0; k < K; ++k) {
-            Walk &sp = W[(size_t)k];
-            if (ti >= cut[(size_t)k + 1]) continue;   // the true walk stepped over this chunk
-            Walk &rep = reps[(size_t)k];
-            while (ti < cut[(size_t)k + 1] && !from[ti]) ti = step(ti, rep);
-            if (!rep.rows.empty()) seg.emplace_back(rep.rows.data(), rep.rows.size());
-            if (ti >= cut[(size_t)k + 1]) continue;
-            size_t q = (size_t)(std::lower_bound(sp.at.begin(), sp.at.end(), ti) - sp.at.begin());
-            if (q < sp.rows.size()) seg.emplace_back(sp.rows.data() + q, sp.rows.size() - q);
-            ti = sp.next;
-        }
-        std::vector<size_t> at(seg.size() + 1, out.rows.size());
-        for (size_t q = 0; q < seg.size(); ++q) at[q + 1] = at[q] + seg[q].second;
-        out.rows.resize(at.back());
-        run_tasks((int64_t)seg.size(), nt, [&](int64_t q) {
-            std::copy(seg[(size_t)q].first, seg[(size_t)q].first + seg[(size_t)q].second, out.rows.begin() + (std::ptrdiff_t)at[(size_t)q]);
-        });
-        for (auto &w : reps) out.pools.push_back(std::move(w.pool));
-        for (auto &w : W) out.pools.push_back(std::move(w.pool));
-    }
-    if (stats_on()) {
-        auto d = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        std::fprintf(stderr, "  compounds: group+kmer %.1f sort %.1f walk %.1f ms (%zu pieces)\n", d(T0, T1), tsort,
-                     d(T2, std::chrono::steady_clock::now()) - tsort, out.pool.size());
+        i = j;
     }
 }
 
@@ -405,19 +317,20 @@ struct Out {
     // doubling); finish() cuts s to what was written
     Text s;
     char *w = nullptr, *e = nullptr;
-    std::string built, fc;   // per-chunk scratch of the row formatters (no thread-local lookups per row)
+    std::string built, core;   // per-chunk scratch of the row formatters (no thread-local lookups per row)
+    size_t used() const { return w ? (size_t)(w - s.data()) : 0; }
     void reserve(size_t n) {
-        const size_t used = w ? (size_t)(w - s.data()) : 0;
-        s.set_size(used);
-        s.grow(used + n);
-        w = s.data() + used;
+        const size_t u = used();
+        s.set_size(u);
+        s.grow(u + n);
+        w = s.data() + u;
         e = s.data() + s.capacity();
     }
     void need(size_t n) {
         if ((size_t)(e - w) < n) reserve(std::max(n, s.capacity()));
     }
     Text finish() {
-        s.set_size(w ? (size_t)(w - s.data()) : 0);
+        s.set_size(used());
         w = e = nullptr;
         return std::move(s);
     }
@@ -455,14 +368,14 @@ struct Out {
         need(24);
         w = int_dec(x, w);
     }
-    void rep(const std::string &m, int64_t times) {
-        for (int64_t k = 0; k < times; ++k) put(m);
+    void rep(const char *m, int64_t len, int64_t times) {
+        for (int64_t k = 0; k < times; ++k) put(m, len);
     }
 };
 
 inline int64_t py_round(double x) { return (int64_t)std::nearbyint(x); }
 
-void comp_entropy(const Rec &r, double comp[4], double &ent) {
+void comp_entropy(const RecRef &r, double comp[4], double &ent) {
     if (r.kmer_stats) {
         comp[0] = comp[1] = comp[2] = comp[3] = 0.0;
         ent = 1.5;
@@ -473,11 +386,11 @@ void comp_entropy(const Rec &r, double comp[4], double &ent) {
         ent = 0.0;
         return;
     }
-    composition_of(r.motif.data(), (int64_t)r.motif.size(), comp);
-    ent = entropy_of(r.motif.data(), (int64_t)r.motif.size());
+    composition_of(r.motif, r.mlen, comp);
+    ent = entropy_of(r.motif, r.mlen);
 }
 
-void row_strfinder(Out &o, const Job &job, const Rec &r, const Rec *partner) {
+void row_strfinder(Out &o, const Job &job, const RecRef &r, const RecRef *partner) {
     const Contig &c = job.contigs[(size_t)r.chrom];
     const Seq &full = c.full;
     const int64_t FL = (int64_t)full.size();
@@ -494,18 +407,18 @@ void row_strfinder(Out &o, const Job &job, const Rec &r, const Rec *partner) {
     o.put(c.name);
     o.c('\t');
     if (partner) {
-        const Rec &p = *partner;
+        const RecRef &p = *partner;
         const int64_t k1 = py_round(r.copies), k2 = py_round(p.copies);
-        std::string core;
-        View a1 = act_of(job, r), a2 = act_of(job, p);
-        if (!a1.empty()) core.append(a1.p, (size_t)a1.n);
-        else for (int64_t k = 0; k < k1; ++k) core += r.motif;
-        if (!a2.empty()) core.append(a2.p, (size_t)a2.n);
-        else for (int64_t k = 0; k < k2; ++k) core += p.motif;
+        std::string &core = o.core;
+        core.clear();
+        if (r.act_len > 0) core.append(r.act, (size_t)r.act_len);
+        else for (int64_t k = 0; k < k1; ++k) core.append(r.motif, (size_t)r.mlen);
+        if (p.act_len > 0) core.append(p.act, (size_t)p.act_len);
+        else for (int64_t k = 0; k < k2; ++k) core.append(p.motif, (size_t)p.mlen);
         o.put(c.name); o.c(':'); o.i(r.start + 1); o.c('-'); o.i(p.end); o.c('\t');
-        o.c('['); o.put(r.motif); o.put("]n+["); o.put(p.motif); o.put("]n\t");
-        o.i((int64_t)r.motif.size()); o.c('['); o.put(r.motif); o.c(']'); o.i(k1); o.c(';');
-        o.i((int64_t)p.motif.size()); o.c('['); o.put(p.motif); o.c(']'); o.i(k2); o.put(",0\t");
+        o.c('['); o.put(r.motif, r.mlen); o.put("]n+["); o.put(p.motif, p.mlen); o.put("]n\t");
+        o.i(r.mlen); o.c('['); o.put(r.motif, r.mlen); o.c(']'); o.i(k1); o.c(';');
+        o.i(p.mlen); o.c('['); o.put(p.motif, p.mlen); o.c(']'); o.i(k2); o.put(",0\t");
         o.i(k1); o.c('/'); o.i(k2); o.c('\t');
         o.put(core); o.put("\t100%\t-\t");
         o.i(k1); o.c(':'); o.i(k2); o.c('\t'); o.i(k1 + k2); o.c('\t');
@@ -513,12 +426,11 @@ void row_strfinder(Out &o, const Job &job, const Rec &r, const Rec *partner) {
         o.put("\t-\n");
         return;
     }
-    const std::string &cons = r.motif;
-    const int64_t ml = (int64_t)cons.size();
+    const int64_t ml = r.mlen;
     const int64_t cc = (int64_t)std::floor(r.copies + 1e-6);
     o.put(c.name); o.c(':'); o.i(r.start + 1); o.c('-'); o.i(r.end); o.c('\t');
-    o.c('['); o.put(cons); o.put("]n\t");
-    o.i(ml); o.c('['); o.put(cons); o.c(']'); o.i(cc); o.c(','); o.i((r.end - r.start) - ml * cc); o.c('\t');
+    o.c('['); o.put(r.motif, ml); o.put("]n\t");
+    o.i(ml); o.c('['); o.put(r.motif, ml); o.c(']'); o.i(cc); o.c(','); o.i((r.end - r.start) - ml * cc); o.c('\t');
     if (std::fabs(r.copies - std::nearbyint(r.copies)) < 1e-6) {
         o.i(py_round(r.copies));
     } else {
@@ -533,10 +445,10 @@ void row_strfinder(Out &o, const Job &job, const Rec &r, const Rec *partner) {
     o.c('\t');
     // core sequence: the actual-sequence slice, or the motif repeated int(copies) times
     std::string &built = o.built;
-    View core = act_of(job, r);
+    View core{r.act, r.act_len};
     if (core.empty()) {
         built.clear();
-        for (int64_t k = 0; k < (int64_t)r.copies; ++k) built += cons;
+        for (int64_t k = 0; k < (int64_t)r.copies; ++k) built.append(r.motif, (size_t)ml);
         core.p = built.data();
         core.n = (int64_t)built.size();
     }
@@ -568,8 +480,78 @@ void row_strfinder(Out &o, const Job &job, const Rec &r, const Rec *partner) {
         if (flanks) { o.put(fl); o.put(core); o.put(fr); } else o.put(core);
     }
     o.c('\t');
-    if (!r.variations.empty()) o.put(r.variations); else o.c('-');
+    if (r.vlen > 0) o.put(r.var, r.vlen); else o.c('-');
     o.c('\n');
+}
+
+// one row of any format; row_id is the VCF record id
+void format_row(Out &o, const Job &job, int fmt, const RecRef &r, const RecRef *partner, int64_t row_id) {
+    double cp[4], ent;
+    const std::string &name = job.contigs[(size_t)r.chrom].name;
+    const int64_t ml = r.mlen;
+    switch (fmt) {
+        case BWTMI_FMT_BED:
+            o.put(name); o.c('\t'); o.i(r.start); o.c('\t'); o.i(r.end);
+            o.c('\t'); o.put(r.motif, ml); o.c('\t'); o.f("%.1f", r.copies); o.c('\t'); o.i(r.tier); o.c('\t');
+            o.f("%.3f", r.mismatch_rate); o.c('\t'); o.c(r.strand); o.c('\n');
+            break;
+        case BWTMI_FMT_VCF:
+            o.put(name); o.c('\t'); o.i(r.start + 1); o.put("\tTR"); o.i(row_id);
+            o.put("\t.\t<TR>\t.\tPASS\tMOTIF="); o.put(r.motif, ml); o.put(";CONS_MOTIF="); o.put(r.motif, ml);
+            o.put(";COPIES="); o.f("%.1f", r.copies); o.put(";TIER="); o.i(r.tier);
+            o.put(";CONF="); o.f("%.2f", r.confidence); o.put(";MM_RATE="); o.f("%.3f", r.mismatch_rate);
+            o.put(";MAX_MM_PER_COPY="); o.i(r.max_mm); o.put(";N_COPIES_EVAL="); o.i(r.n_eval);
+            o.put(";STRAND="); o.c(r.strand); o.c('\n');
+            break;
+        case BWTMI_FMT_TRF_TABLE:
+            comp_entropy(r, cp, ent);
+            o.i(r.start); o.put("--"); o.i(r.end); o.c('\t'); o.i(ml); o.c('\t'); o.f("%.1f", r.copies);
+            o.c('\t'); o.i(ml); o.c('\t'); o.f("%.0f", r.pmatch); o.c('\t'); o.f("%.0f", r.pindel); o.c('\t');
+            o.i(r.score); o.c('\t'); o.f("%.0f", cp[0]); o.c('\t'); o.f("%.0f", cp[1]); o.c('\t');
+            o.f("%.0f", cp[2]); o.c('\t'); o.f("%.0f", cp[3]); o.c('\t'); o.f("%.2f", ent); o.c('\n');
+            break;
+        case BWTMI_FMT_TRF_DAT:
+            comp_entropy(r, cp, ent);
+            o.i(r.start); o.c(' '); o.i(r.end); o.c(' '); o.i(ml); o.c(' '); o.f("%.1f", r.copies); o.c(' ');
+            o.i(ml); o.c(' '); o.f("%.0f", r.pmatch); o.c(' '); o.f("%.0f", r.pindel); o.c(' ');
+            o.i(r.score); o.c(' '); o.f("%.0f", cp[0]); o.c(' '); o.f("%.0f", cp[1]); o.c(' ');
+            o.f("%.0f", cp[2]); o.c(' '); o.f("%.0f", cp[3]); o.c(' '); o.f("%.2f", ent); o.c(' ');
+            o.put(r.motif, ml); o.c(' ');
+            if (r.act_len > 0) o.put(r.act, r.act_len); else o.rep(r.motif, ml, (int64_t)r.copies);
+            o.c('\n');
+            break;
+        default:   // STRfinder
+            row_strfinder(o, job, r, partner);
+    }
+}
+
+// rows (ordered) appended to o; off (may be null) receives the byte offset of
+// every row and of the end
+void format_rows(Out &o, const Job &job, int fmt, const std::vector<FRow> &rows, int64_t id0, std::vector<size_t> *off) {
+    // a row's flanks and core are bytes of its contig at random distances
+    // from the last row's: their lines are requested a few rows ahead
+    constexpr size_t kAhead = 6;
+    auto prefetch_row = [&](const RecRef &r) {
+        const Seq &full = job.contigs[(size_t)r.chrom].full;
+        if (full.empty()) return;
+        const int64_t FL = (int64_t)full.size();
+        const int64_t s0 = std::min(std::max<int64_t>(0, r.start - 30), FL - 1), e0 = std::min(std::max<int64_t>(0, r.end), FL - 1);
+        __builtin_prefetch(full.data() + s0);
+        __builtin_prefetch(full.data() + s0 + 64);
+        __builtin_prefetch(full.data() + e0);
+    };
+    const bool str = fmt == BWTMI_FMT_STRFINDER;
+    const size_t n = rows.size();
+    o.reserve(n * 256);
+    if (off) off->reserve(off->size() + n + 1);
+    if (str)
+        for (size_t k = 0; k < std::min(n, kAhead); ++k) prefetch_row(*rows[k].r);
+    for (size_t k = 0; k < n; ++k) {
+        if (str && k + kAhead < n) prefetch_row(*rows[k + kAhead].r);
+        if (off) off->push_back(o.used());
+        format_row(o, job, fmt, *rows[k].r, rows[k].p, id0 + (int64_t)k);
+    }
+    if (off) off->push_back(o.used());
 }
 
 const char *kVcfHeader =
@@ -585,71 +567,41 @@ const char *kVcfHeader =
     "##INFO=<ID=STRAND,Number=1,Type=String,Description=\"Strand of canonical motif (+/-)\">\n"
     "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
 
+// the records of one fold unit that has any, and what the pre-pass found for them
+struct UnitPlan {
+    int32_t unit = 0;
+    // one chromosome, consecutive in the job's records, in start order: walked
+    // and formatted in parallel chunks.  Anything else (records handed in in
+    // another order, a unit of several chromosomes) is one chunk on one thread.
+    bool regular = true;
+    size_t n = 0;                        // regular: its records
+    std::vector<const Rec *> list;       // not regular: the unit's records in the job's order
+    std::vector<std::pair<size_t, RecRef>> found;   // k-mer pieces with the index of the record they follow
+    std::vector<RecRef> pieces;          // regular: the same by start, and where they go
+    std::vector<size_t> ppos;
+    std::vector<Long> longs;
+    int64_t base = 0;                    // VCF id of the unit's first row
+    Merged M;
+};
+
 }  // namespace
 
-// Rows are formatted in parallel, in chunks of consecutive rows; each chunk is
-// one part of the output, so concatenating the parts gives the file.
+// Records to bytes in one pass.  A pre-pass over the records finds the fold
+// units' runs, the k-mer pieces behind 3-mer records and the > 10 bp motifs.
+// Then chunks of consecutive records of one unit are walked for compounds as if
+// the walk arrived at their first index, ordered and formatted, each into its
+// own part, while they are in cache.  Chunk edges lie where the start grows, so
+// no run of equal starts spans two chunks.  The chunks are committed in order:
+// when the true walk enters a chunk elsewhere than at its first index (a step
+// of the chunk before consumed records of this one), it is walked again from
+// there until both walks step from the same index at the beginning of a run of
+// equal starts -- from then on they are the same walk -- and only the rows up
+// to there are formatted again; the bytes behind them are kept.
 void render_rows(Job &job, int fmt, const int64_t *row_base, Rendered &out,
                  const std::function<void(size_t)> *on_part) {
-    auto t0 = std::chrono::steady_clock::now();
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
     job.assign_units();
-    Compound comp;
-    std::vector<Row> rows;
-    if (fmt == BWTMI_FMT_STRFINDER) {
-        BWTMI_STAGE("bwtmi:compounds");
-        detect_compounds(job, job.final_recs, comp, host_threads(job.params));
-        rows.swap(comp.rows);
-    } else {
-        rows.reserve(job.final_recs.size());
-        for (const Rec &r : job.final_recs) rows.push_back(row_of(job, &r, nullptr));
-    }
-    // sorted(all_repeats, key=lambda r: (natural_sort_key(r.chrom), r.start, r.end)) (bwt.py:4150)
-    // The rows arrive ordered by (unit, start) in the usual case (one contig
-    // per unit): then only runs of equal (unit, start) need a stable order by
-    // end, which equals the full stable sort.
-    auto unit_start_lt = [](const Row &a, const Row &b) {
-        if (a.unit != b.unit) return a.unit < b.unit;
-        return a.start < b.start;
-    };
-    const int nt = host_threads(job.params);
-    const size_t NR = rows.size();
-    const int RC = NR > 8192 ? 4 * nt : 1;
-    std::vector<uint8_t> chunk_ok((size_t)RC, 1);
-    run_tasks(RC, nt, [&](int64_t t) {   // sorted by (unit, start)?  chunk t checks pairs ending in it
-        const size_t a = std::max<size_t>(1, NR * (size_t)t / (size_t)RC), b = NR * (size_t)(t + 1) / (size_t)RC;
-        for (size_t k = a; k < b; ++k)
-            if (unit_start_lt(rows[k], rows[k - 1])) { chunk_ok[(size_t)t] = 0; return; }
-    });
-    bool by_unit_start = true;
-    for (auto v : chunk_ok) by_unit_start = by_unit_start && v;
-    if (by_unit_start) {
-        run_tasks(RC, nt, [&](int64_t t) {   // chunk t orders the equal-(unit, start) runs that begin in it
-            size_t i = NR * (size_t)t / (size_t)RC;
-            const size_t b = NR * (size_t)(t + 1) / (size_t)RC;
-            while (i > 0 && i < b && !unit_start_lt(rows[i - 1], rows[i])) ++i;
-            while (i < b) {
-                size_t j = i + 1;
-                while (j < NR && !unit_start_lt(rows[i], rows[j])) ++j;   // equal (unit, start)
-                for (size_t a = i + 1; a < j; ++a) {   // stable insertion sort by end (runs are short)
-                    const Row x = rows[a];
-                    size_t q = a;
-                    while (q > i && rows[q - 1].end > x.end) {
-                        rows[q] = rows[q - 1];
-                        --q;
-                    }
-                    rows[q] = x;
-                }
-                i = j;
-            }
-        });
-    } else {
-        std::stable_sort(rows.begin(), rows.end(), [](const Row &a, const Row &b) {
-            if (a.unit != b.unit) return a.unit < b.unit;
-            if (a.start != b.start) return a.start < b.start;
-            return a.end < b.end;
-        });
-    }
-    auto t1 = std::chrono::steady_clock::now();
     std::string head;
     switch (fmt) {
         case BWTMI_FMT_BED:
@@ -671,135 +623,431 @@ void render_rows(Job &job, int fmt, const int64_t *row_base, Rendered &out,
         default:
             fail(BWTMI_E_ARG, "unknown output format %d", fmt);
     }
-    // chunks of <= CH consecutive rows that never span two fold units; VCF row
-    // ids are row_base[unit] + rank within the unit (global index when the
-    // caller renders only its own shard), else the local index
-    const int64_t n = (int64_t)rows.size();
-    // >= 8 chunks per thread while that keeps them >= 256 rows (a 40k-row shard
-    // in 8192-row chunks kept 5 of 16 threads busy; in 1024-row chunks, 2 or 3
-    // chunks a thread, the last wave left threads idle)
-    const int64_t CH = std::max<int64_t>(256, std::min<int64_t>(8192, n / (8 * (int64_t)host_threads(job.params)) + 1));
-    auto unit_of = [&](int64_t k) { return rows[(size_t)k].unit; };
-    struct Chunk { int64_t a, b, id0; int32_t unit; };
+    const bool str = fmt == BWTMI_FMT_STRFINDER;
+    const int nt = host_threads(job.params);
+    auto unit_of = [&](const Rec &r) { return job.contigs[(size_t)r.chrom].unit; };
+    // the k-mer pieces behind a 3-mer record ending at `end` (bwt.py:4011-4024)
+    auto pieces_behind = [&](int32_t chrom, int64_t end, const char *motif, size_t q, std::vector<RecRef> &kr,
+                             std::vector<std::pair<size_t, RecRef>> &out) {
+        const Seq &full = job.contigs[(size_t)chrom].full;
+        if (full.empty()) return;
+        const int64_t a = end, b = std::min<int64_t>((int64_t)full.size(), end + 50);
+        if (a >= b) return;
+        kr.clear();
+        kmer_scan(job, chrom, a, b, kr);
+        for (const RecRef &x : kr)
+            if (std::memcmp(x.motif, motif, 3) != 0) out.emplace_back(q, x);
+    };
+
+    // ---- pre-pass: the fold units' runs, the k-mer pieces behind 3-mer records
+    // and the > 10 bp motifs.  Over the fold's survivors when the job still holds
+    // them (each unit is one run of one chromosome; 32 bytes a record), else
+    // over the records.
+    std::optional<StageRange> sr;
+    sr.emplace("bwtmi:compounds");
+    std::vector<UnitPlan> plans;
+    size_t NR = 0, n_pieces = 0, n_longs = 0;
+    const std::shared_ptr<Survivors> held = job.survivors();   // (kept for the pass whatever another thread does)
+    const Survivors *sv = held.get();
+    if (sv) {
+        struct Sub {
+            size_t k, a, b;
+            bool sorted = true;
+            std::vector<std::pair<size_t, RecRef>> pieces;
+            std::vector<Long> longs;
+        };
+        std::vector<Sub> subs;
+        const size_t per = std::max<size_t>(1024, sv->size() / (size_t)(4 * std::max(1, nt)) + 1);
+        for (size_t k = 0; k < sv->units(); ++k)
+            for (size_t a = 0, n = sv->unit_size(k); a < n; a += per) subs.push_back({k, a, std::min(n, a + per), true, {}, {}});
+        run_tasks((int64_t)subs.size(), nt, [&](int64_t t) {
+            Sub &S = subs[(size_t)t];
+            std::vector<RecRef> kr;
+            int64_t s, e, prev = INT64_MIN;
+            int32_t ml;
+            if (S.a > 0) sv->span(S.k, S.a - 1, prev, e, ml);
+            for (size_t i = S.a; i < S.b; ++i) {
+                sv->span(S.k, i, s, e, ml);
+                S.sorted = S.sorted && s >= prev;
+                prev = s;
+                if (!str) continue;
+                if (ml > 10) S.longs.push_back({s, e, 0});
+                if (ml == 3) pieces_behind(sv->unit_chrom(S.k), e, sv->view(S.k, i).motif, i, kr, S.pieces);
+            }
+        });
+        bool sorted = true;
+        for (const Sub &S : subs) sorted = sorted && S.sorted;
+        if (!sorted) {
+            sv = nullptr;   // (the fold leaves every unit in start order: not expected)
+        } else {
+            plans.resize(sv->units());
+            for (size_t k = 0; k < sv->units(); ++k) {
+                plans[k].unit = sv->unit_id(k);
+                plans[k].n = sv->unit_size(k);
+                plans[k].M.sv = sv;
+                plans[k].M.su = k;
+                plans[k].M.chrom = sv->unit_chrom(k);
+                NR += plans[k].n;
+            }
+            for (Sub &S : subs) {
+                UnitPlan &U = plans[S.k];
+                U.found.insert(U.found.end(), S.pieces.begin(), S.pieces.end());
+                U.longs.insert(U.longs.end(), S.longs.begin(), S.longs.end());
+            }
+        }
+    }
+    if (!sv) {
+        const RecVec &recs = job.recs();
+        NR = recs.size();
+        const int PC = NR > 8192 ? 4 * std::max(1, nt) : 1;
+        struct Pre {
+            bool disorder = false;              // a unit after a larger one
+            std::vector<size_t> ubounds;        // q: recs[q] begins a larger unit
+            std::vector<int32_t> irregular;     // units with two chromosomes, or starts out of order
+            std::vector<std::pair<size_t, RecRef>> pieces;
+            std::vector<std::pair<size_t, Long>> longs;
+        };
+        std::vector<Pre> pre((size_t)PC);
+        run_tasks(PC, nt, [&](int64_t t) {
+            Pre &P = pre[(size_t)t];
+            std::vector<RecRef> kr;
+            for (size_t q = NR * (size_t)t / (size_t)PC; q < NR * (size_t)(t + 1) / (size_t)PC; ++q) {
+                const Rec &r = recs[q];
+                if (q > 0) {
+                    const Rec &pr = recs[q - 1];
+                    const int32_t u = unit_of(r), pu = unit_of(pr);
+                    if (u < pu) P.disorder = true;
+                    else if (u > pu) P.ubounds.push_back(q);
+                    else if (r.chrom != pr.chrom || r.start < pr.start) P.irregular.push_back(u);
+                }
+                if (!str) continue;
+                if (r.motif.size() > 10) P.longs.push_back({q, Long{r.start, r.end, 0}});
+                if (r.motif.size() == 3) pieces_behind(r.chrom, r.end, r.motif.data(), q, kr, P.pieces);
+            }
+        });
+        bool disorder = false;
+        for (const Pre &P : pre) disorder = disorder || P.disorder;
+        if (disorder) {   // the units' records are gathered, each unit one chunk
+            std::vector<int32_t> slot((size_t)std::max(1, job.nunits), -1);
+            std::vector<std::vector<const Rec *>> lists((size_t)std::max(1, job.nunits));
+            for (const Rec &r : recs) lists[(size_t)unit_of(r)].push_back(&r);
+            for (int32_t u = 0; u < job.nunits; ++u)
+                if (!lists[(size_t)u].empty()) {
+                    slot[(size_t)u] = (int32_t)plans.size();
+                    plans.emplace_back();
+                    plans.back().unit = u;
+                    plans.back().regular = false;
+                    plans.back().list.swap(lists[(size_t)u]);
+                }
+            for (Pre &P : pre)
+                for (auto &pc : P.pieces) plans[(size_t)slot[(size_t)unit_of(recs[pc.first])]].found.push_back(pc);
+        } else if (NR > 0) {
+            std::vector<size_t> runs{0};
+            for (const Pre &P : pre) runs.insert(runs.end(), P.ubounds.begin(), P.ubounds.end());
+            runs.push_back(NR);
+            std::vector<uint8_t> irr((size_t)job.nunits, 0);
+            for (const Pre &P : pre)
+                for (int32_t u : P.irregular) irr[(size_t)u] = 1;
+            plans.resize(runs.size() - 1);
+            for (size_t k = 0; k + 1 < runs.size(); ++k) {
+                UnitPlan &U = plans[k];
+                U.unit = unit_of(recs[runs[k]]);
+                U.n = runs[k + 1] - runs[k];
+                U.regular = !irr[(size_t)U.unit];
+                U.M.main = recs.data() + runs[k];
+                U.M.chrom = recs[runs[k]].chrom;
+                if (!U.regular)
+                    for (size_t q = runs[k]; q < runs[k + 1]; ++q) U.list.push_back(&recs[q]);
+            }
+            // pieces and long motifs arrive by record index: each goes to its run
+            size_t k = 0;
+            for (Pre &P : pre)
+                for (auto &pc : P.pieces) {
+                    while (pc.first >= runs[k + 1]) ++k;
+                    plans[k].found.push_back(pc);
+                }
+            k = 0;
+            for (Pre &P : pre)
+                for (auto &lg : P.longs) {
+                    while (lg.first >= runs[k + 1]) ++k;
+                    if (plans[k].regular) plans[k].longs.push_back(lg.second);
+                }
+        }
+    }
+    int64_t before = 0;
+    size_t n_irregular = 0;
+    for (UnitPlan &U : plans) {
+        const size_t n_main = U.regular ? U.n : U.list.size();
+        U.base = row_base ? row_base[U.unit] : before;
+        before += (int64_t)n_main;
+        n_pieces += U.found.size();
+        if (!U.regular) {
+            ++n_irregular;
+            continue;
+        }
+        n_longs += U.longs.size();
+        for (size_t q = 0; q < U.longs.size(); ++q)
+            U.longs[q].pe = q ? std::max(U.longs[q - 1].pe, U.longs[q].e) : U.longs[q].e;
+        U.M.n_main = U.n;
+        U.M.longs = U.longs.data();
+        U.M.nl = U.longs.size();
+        // the pieces by start (stably), each behind the records of equal start
+        std::stable_sort(U.found.begin(), U.found.end(),
+                         [](const auto &x, const auto &y) { return x.second.start < y.second.start; });
+        for (size_t q = 0; q < U.found.size(); ++q) {
+            U.pieces.push_back(U.found[q].second);
+            U.ppos.push_back(U.M.mains_upto(U.found[q].second.start) + q);
+        }
+        U.M.pieces = U.pieces.data();
+        U.M.ppos = U.ppos.data();
+        U.M.np = U.pieces.size();
+    }
+    sr.reset();
+    const auto t1 = clk::now();
+
+    // ---- chunks: <= CH consecutive merged records of one unit, cut where the
+    // start grows.  BWTMI_RENDER_CHUNK sets CH; by default >= 8 chunks per
+    // thread while that keeps them >= 256 rows (a 40k-row shard in 8192-row
+    // chunks kept 5 of 16 threads busy; in 1024-row chunks, 2 or 3 chunks a
+    // thread, the last wave left threads idle)
+    const int64_t n_all = (int64_t)(NR + n_pieces);
+    const int64_t knob_ch = knob(KN_RENDER_CHUNK);
+    const size_t CH = (size_t)(knob_ch > 0 ? knob_ch
+                                           : std::max<int64_t>(256, std::min<int64_t>(8192, n_all / (8 * (int64_t)nt) + 1)));
+    struct Chunk {
+        size_t plan, ma, mb;
+        // what a later walk from inside the chunk needs: the index each row was
+        // emitted from, the rows' starts and byte offsets (both in output order,
+        // which differs from the walk's only inside runs of equal start)
+        std::vector<uint32_t> at;
+        std::vector<size_t> off;
+        std::vector<int64_t> rstart;
+        size_t next = 0;
+    };
     std::vector<Chunk> chunks;
-    for (int64_t a = 0; a < n;) {
-        const int32_t un = unit_of(a);
-        int64_t e = a;
-        if (by_unit_start)   // rows ordered by unit: the unit's run ends at the first larger unit
-            e = (int64_t)(std::partition_point(rows.begin() + (std::ptrdiff_t)a, rows.end(),
-                                               [un](const Row &x) { return x.unit == un; }) - rows.begin());
-        else
-            while (e < n && unit_of(e) == un) ++e;
-        const int64_t base = row_base ? row_base[un] : a;
-        for (int64_t c = a; c < e; c += CH) chunks.push_back({c, std::min(e, c + CH), base + (c - a), un});
-        a = e;
+    for (size_t p = 0; p < plans.size(); ++p) {
+        const UnitPlan &U = plans[p];
+        if (!U.regular) {
+            chunks.push_back({p, 0, 0, {}, {}, {}, 0});
+            continue;
+        }
+        const size_t N = U.M.size();
+        for (size_t a = 0; a < N;) {
+            size_t b = std::min(N, a + CH);
+            while (b < N && U.M.start_at(b) == U.M.start_at(b - 1)) ++b;
+            chunks.push_back({p, a, b, {}, {}, {}, 0});
+            a = b;
+        }
     }
     out.header = std::move(head);
     out.parts.clear();
     out.parts.resize(chunks.size());
     out.part_unit.resize(chunks.size());
-    for (size_t q = 0; q < chunks.size(); ++q) out.part_unit[q] = chunks[q].unit;
-    auto t2 = std::chrono::steady_clock::now();
-    std::optional<StageRange> fr;
-    fr.emplace("bwtmi:format");
-    // BWTMI_STATS=3: per-chunk timeline (thread, formatting, on_part) of this stage
-    struct Tl { double a, b, c; size_t th; };
-    std::vector<Tl> tl(stats_on(3) ? chunks.size() : 0);
-    auto now_ms = [t2] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count(); };
-    run_tasks((int64_t)chunks.size(), host_threads(job.params), [&](int64_t ck) {
-        if (!tl.empty()) { tl[(size_t)ck].a = now_ms(); tl[(size_t)ck].th = std::hash<std::thread::id>()(std::this_thread::get_id()); }
-        Out o;
-        const Chunk &C = chunks[(size_t)ck];
-        const int64_t a = C.a, b = C.b;
-        o.reserve((size_t)(b - a) * 256);
-        double cp[4], ent;
-        // a row's flanks and core are bytes of its contig at random distances
-        // from the last row's: their lines are requested a few rows ahead
-        constexpr int64_t kAhead = 6;
-        auto prefetch_row = [&](int64_t k) {
-            const Rec &r = *rows[(size_t)k].r;
-            const Seq &full = job.contigs[(size_t)r.chrom].full;
-            if (full.empty()) return;
-            const int64_t FL = (int64_t)full.size();
-            const int64_t s0 = std::min(std::max<int64_t>(0, r.start - 30), FL - 1), e0 = std::min(std::max<int64_t>(0, r.end), FL - 1);
-            __builtin_prefetch(full.data() + s0);
-            __builtin_prefetch(full.data() + s0 + 64);
-            __builtin_prefetch(full.data() + e0);
-        };
-        if (fmt == BWTMI_FMT_STRFINDER)
-            for (int64_t k = a; k < std::min(b, a + kAhead); ++k) prefetch_row(k);
-        for (int64_t k = a; k < b; ++k) {
-            if (fmt == BWTMI_FMT_STRFINDER && k + kAhead < b) prefetch_row(k + kAhead);
-            const Rec &r = *rows[(size_t)k].r;
-            const int64_t row_id = C.id0 + (k - a);
-            switch (fmt) {
-                case BWTMI_FMT_BED:
-                    o.put(job.contigs[(size_t)r.chrom].name); o.c('\t'); o.i(r.start); o.c('\t'); o.i(r.end);
-                    o.c('\t'); o.put(r.motif); o.c('\t'); o.f("%.1f", r.copies); o.c('\t'); o.i(r.tier); o.c('\t');
-                    o.f("%.3f", r.mismatch_rate); o.c('\t'); o.c(r.strand); o.c('\n');
-                    break;
-                case BWTMI_FMT_VCF:
-                    o.put(job.contigs[(size_t)r.chrom].name); o.c('\t'); o.i(r.start + 1); o.put("\tTR"); o.i(row_id);
-                    o.put("\t.\t<TR>\t.\tPASS\tMOTIF="); o.put(r.motif); o.put(";CONS_MOTIF="); o.put(r.motif);
-                    o.put(";COPIES="); o.f("%.1f", r.copies); o.put(";TIER="); o.i(r.tier);
-                    o.put(";CONF="); o.f("%.2f", r.confidence); o.put(";MM_RATE="); o.f("%.3f", r.mismatch_rate);
-                    o.put(";MAX_MM_PER_COPY="); o.i(r.max_mm); o.put(";N_COPIES_EVAL="); o.i(r.n_eval);
-                    o.put(";STRAND="); o.c(r.strand); o.c('\n');
-                    break;
-                case BWTMI_FMT_TRF_TABLE: {
-                    comp_entropy(r, cp, ent);
-                    const int64_t ml = (int64_t)r.motif.size();
-                    o.i(r.start); o.put("--"); o.i(r.end); o.c('\t'); o.i(ml); o.c('\t'); o.f("%.1f", r.copies);
-                    o.c('\t'); o.i(ml); o.c('\t'); o.f("%.0f", r.pmatch); o.c('\t'); o.f("%.0f", r.pindel); o.c('\t');
-                    o.i(r.score); o.c('\t'); o.f("%.0f", cp[0]); o.c('\t'); o.f("%.0f", cp[1]); o.c('\t');
-                    o.f("%.0f", cp[2]); o.c('\t'); o.f("%.0f", cp[3]); o.c('\t'); o.f("%.2f", ent); o.c('\n');
-                    break;
-                }
-                case BWTMI_FMT_TRF_DAT: {
-                    comp_entropy(r, cp, ent);
-                    const int64_t ml = (int64_t)r.motif.size();
-                    o.i(r.start); o.c(' '); o.i(r.end); o.c(' '); o.i(ml); o.c(' '); o.f("%.1f", r.copies); o.c(' ');
-                    o.i(ml); o.c(' '); o.f("%.0f", r.pmatch); o.c(' '); o.f("%.0f", r.pindel); o.c(' ');
-                    o.i(r.score); o.c(' '); o.f("%.0f", cp[0]); o.c(' '); o.f("%.0f", cp[1]); o.c(' ');
-                    o.f("%.0f", cp[2]); o.c(' '); o.f("%.0f", cp[3]); o.c(' '); o.f("%.2f", ent); o.c(' ');
-                    o.put(r.motif); o.c(' ');
-                    View av = act_of(job, r);
-                    if (!av.empty()) o.put(av); else o.rep(r.motif, (int64_t)r.copies);
-                    o.c('\n');
-                    break;
-                }
-                default:   // STRfinder
-                    row_strfinder(o, job, r, rows[(size_t)k].partner);
+    for (size_t q = 0; q < chunks.size(); ++q) out.part_unit[q] = plans[chunks[q].plan].unit;
+    const auto t2 = clk::now();
+
+    // ---- the pass
+    sr.emplace("bwtmi:format");
+    std::atomic<size_t> n_rows{0};
+    size_t rewalked_chunks = 0, rewalked_rows = 0;
+    // a unit that is not one sorted run: the reference's steps on one thread
+    auto whole_unit = [&](const UnitPlan &U, Text &part) {
+        std::vector<int32_t> order;                       // chromosomes by first record
+        std::vector<std::vector<const Rec *>> by(job.contigs.size());
+        for (const Rec *r : U.list) {
+            if (by[(size_t)r->chrom].empty()) order.push_back(r->chrom);
+            by[(size_t)r->chrom].push_back(r);
+        }
+        auto by_start = [](const Rec *x, const Rec *y) { return x->start < y->start; };
+        std::deque<Merged> ms;
+        std::deque<Walk> walks;
+        std::deque<std::vector<RecRef>> pieces;
+        std::deque<std::vector<size_t>> ppos;
+        std::deque<std::vector<Long>> longs;
+        std::vector<FRow> rows;
+        for (int32_t ch : order) {
+            std::vector<const Rec *> &rs = by[(size_t)ch];
+            std::stable_sort(rs.begin(), rs.end(), by_start);
+            pieces.emplace_back();
+            ppos.emplace_back();
+            longs.emplace_back();
+            std::vector<std::pair<size_t, RecRef>> found;
+            for (const auto &pc : U.found)
+                if (pc.second.chrom == ch) found.push_back(pc);
+            std::stable_sort(found.begin(), found.end(),
+                             [](const auto &x, const auto &y) { return x.second.start < y.second.start; });
+            for (size_t q = 0; q < found.size(); ++q) {
+                pieces.back().push_back(found[q].second);
+                ppos.back().push_back((size_t)(std::upper_bound(rs.begin(), rs.end(), found[q].second.start,
+                                                                [](int64_t s, const Rec *r) { return s < r->start; }) -
+                                               rs.begin()) + q);
+            }
+            if (str)
+                for (const Rec *r : rs)
+                    if (r->motif.size() > 10)
+                        longs.back().push_back({r->start, r->end, longs.back().empty() ? r->end : std::max(longs.back().back().pe, r->end)});
+            ms.emplace_back();
+            Merged &M = ms.back();
+            M.list = rs.data();
+            M.n_main = rs.size();
+            M.pieces = pieces.back().data();
+            M.ppos = ppos.back().data();
+            M.np = pieces.back().size();
+            M.longs = longs.back().data();
+            M.nl = longs.back().size();
+            M.chrom = ch;
+            walks.emplace_back(job, M, 0, M.size());
+            Walk &w = walks.back();
+            for (size_t i = 0; i < M.size();) {
+                if (str) i = w.step(i);
+                else w.plain(i++);
             }
         }
-        out.parts[(size_t)ck] = o.finish();
+        for (const Walk &w : walks) w.resolve(rows);
+        // sorted(key=(start, end)) within the unit (bwt.py:4150)
+        std::stable_sort(rows.begin(), rows.end(), [](const FRow &x, const FRow &y) {
+            return x.r->start != y.r->start ? x.r->start < y.r->start : x.r->end < y.r->end;
+        });
+        Out o;
+        format_rows(o, job, fmt, rows, U.base, nullptr);
+        part = o.finish();
+        n_rows.fetch_add(rows.size(), std::memory_order_relaxed);
+    };
+    auto chunk_task = [&](size_t ck) {
+        Chunk &C = chunks[ck];
+        const UnitPlan &U = plans[C.plan];
+        if (!U.regular) {
+            whole_unit(U, out.parts[ck]);
+            return;
+        }
+        Walk w(job, U.M, C.ma, C.mb - C.ma);
+        size_t i = C.ma;
+        while (i < C.mb) {
+            if (str) i = w.step(i);
+            else w.plain(i++);
+        }
+        C.next = i;
+        std::vector<FRow> rows;
+        rows.reserve(w.rows.size());
+        w.resolve(rows);
+        order_equal_starts(rows);
+        Out o;
+        format_rows(o, job, fmt, rows, U.base + (int64_t)C.ma, str ? &C.off : nullptr);
+        out.parts[ck] = o.finish();
+        if (str) {
+            C.at.swap(w.at);
+            C.rstart.reserve(rows.size());
+            for (const FRow &r : rows) C.rstart.push_back(r.r->start);
+        }
+        n_rows.fetch_add(rows.size(), std::memory_order_relaxed);
+    };
+    // the true walk enters chunk ck at ti (inside it, not at its first index)
+    auto rewalk = [&](size_t ck, size_t ti) -> size_t {
+        Chunk &C = chunks[ck];
+        const UnitPlan &U = plans[C.plan];
+        Walk w(job, U.M, ti);
+        size_t i = ti, keep = C.at.size();   // keep: the first row whose bytes stay
+        std::vector<FRow> rows;
+        while (i < C.mb) {
+            const uint32_t rel = (uint32_t)(i - C.ma);
+            const size_t q = (size_t)(std::lower_bound(C.at.begin(), C.at.end(), rel) - C.at.begin());
+            // q >= 1: the first walk stepped from the chunk's first index, before ti
+            if (q < C.at.size() && C.at[q] == rel && C.rstart[q] > C.rstart[q - 1] &&
+                (w.rows.empty() || C.rstart[q] > w.ref(w.rows.back().r)->start)) {
+                keep = q;
+                break;
+            }
+            i = w.step(i);
+        }
+        w.resolve(rows);
+        order_equal_starts(rows);
+        Out o;
+        format_rows(o, job, fmt, rows, 0, nullptr);
+        const Text &old = out.parts[ck];
+        if (keep < C.at.size()) o.put(old.data() + C.off[keep], (int64_t)(old.size() - C.off[keep]));
+        n_rows.fetch_add(rows.size(), std::memory_order_relaxed);
+        n_rows.fetch_sub(keep, std::memory_order_relaxed);
+        out.parts[ck] = o.finish();
+        ++rewalked_chunks;
+        rewalked_rows += rows.size();
+        return keep < C.at.size() ? C.next : i;
+    };
+    // chunks are committed in order, by whichever thread finds the next one
+    // done: a part is final (on_part) once the walk before it is known
+    std::mutex mu;
+    std::vector<uint8_t> done(chunks.size(), 0);
+    size_t frontier = 0, ti = 0;
+    bool committing = false;
+    auto commit = [&](size_t ck) {
+        Chunk &C = chunks[ck];
+        if (str && plans[C.plan].regular) {
+            if (C.ma == 0) ti = 0;
+            if (ti >= C.mb) {   // the walk stepped over the whole chunk
+                n_rows.fetch_sub(C.at.size(), std::memory_order_relaxed);
+                rewalked_chunks += 1;
+                out.parts[ck] = Text();
+            } else if (ti != C.ma) {
+                ti = rewalk(ck, ti);
+            } else {
+                ti = C.next;
+            }
+            std::vector<uint32_t>().swap(C.at);
+            std::vector<size_t>().swap(C.off);
+            std::vector<int64_t>().swap(C.rstart);
+        }
+        if (on_part) (*on_part)(ck);
+    };
+    // BWTMI_STATS=3: per-chunk timeline (thread, walk + formatting, commit) of the pass
+    struct Tl { double a, b, c0, c1; size_t th, cth; };
+    std::vector<Tl> tl(stats_on(3) ? chunks.size() : 0);
+    auto now_ms = [t2] { return std::chrono::duration<double, std::milli>(clk::now() - t2).count(); };
+    auto this_th = [] { return std::hash<std::thread::id>()(std::this_thread::get_id()); };
+    run_tasks((int64_t)chunks.size(), nt, [&](int64_t ck) {
+        if (!tl.empty()) { tl[(size_t)ck].a = now_ms(); tl[(size_t)ck].th = this_th(); }
+        chunk_task((size_t)ck);
         if (!tl.empty()) tl[(size_t)ck].b = now_ms();
-        if (on_part) (*on_part)((size_t)ck);
-        if (!tl.empty()) tl[(size_t)ck].c = now_ms();
+        std::unique_lock<std::mutex> lk(mu);
+        done[(size_t)ck] = 1;
+        if (committing) return;
+        committing = true;
+        while (frontier < chunks.size() && done[frontier]) {
+            const size_t f = frontier;
+            lk.unlock();
+            if (!tl.empty()) { tl[f].c0 = now_ms(); tl[f].cth = this_th(); }
+            commit(f);
+            if (!tl.empty()) tl[f].c1 = now_ms();
+            lk.lock();
+            ++frontier;
+        }
+        committing = false;
     });
-    fr.reset();
-    auto t3 = std::chrono::steady_clock::now();
+    sr.reset();
+    const auto t3 = clk::now();
     if (!tl.empty()) {
-        std::map<size_t, std::pair<double, double>> busy;   // thread -> (formatting, on_part)
+        std::map<size_t, std::pair<double, double>> busy;   // thread -> (walk + formatting, commit with on_part)
         double first = 1e30, last = 0, lastfmt = 0;
         for (const Tl &x : tl) {
             busy[x.th].first += x.b - x.a;
-            busy[x.th].second += x.c - x.b;
+            busy[x.cth].second += x.c1 - x.c0;
             first = std::min(first, x.a);
-            last = std::max(last, x.c);
+            last = std::max(last, x.c1);
             lastfmt = std::max(lastfmt, x.b);
         }
         std::string per;
         for (auto &kv : busy) per += " " + std::to_string((int)(kv.second.first * 100) / 100.0).substr(0, 4) + "/" +
                                      std::to_string((int)(kv.second.second * 100) / 100.0).substr(0, 4);
         std::fprintf(stderr, "  format timeline: %zu chunks, first start %.2f, last format end %.2f, last end %.2f ms; "
-                     "threads (format/on_part ms):%s\n", tl.size(), first, lastfmt, last, per.c_str());
+                     "threads (format/commit ms):%s\n", tl.size(), first, lastfmt, last, per.c_str());
     }
     job.stage_ms[6] = std::chrono::duration<double, std::milli>(t3 - t0).count();
     if (stats_on()) {
         auto d = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        std::fprintf(stderr, "  render: compounds+sort %.1f chunking %.1f format %.1f ms (%zu rows)\n", d(t0, t1),
-                     d(t1, t2), d(t2, t3), rows.size());
+        if (str)
+            std::fprintf(stderr, "  compounds: pre-pass %.1f ms (%zu pieces, %zu long motifs; %zu units, %zu not one sorted run); "
+                         "walked again from inside: %zu chunks, %zu rows\n", d(t0, t1), n_pieces, n_longs, plans.size(),
+                         n_irregular, rewalked_chunks, rewalked_rows);
+        std::fprintf(stderr, "  render: pre-pass %.1f chunking %.1f pass %.1f ms (%zu chunks, %zu rows)\n", d(t0, t1),
+                     d(t1, t2), d(t2, t3), chunks.size(), n_rows.load());
     }
 }
 

@@ -572,7 +572,8 @@ int bwtmi_job_write_units(bwtmi_job *job, const char *path, const int64_t *offse
 /* the same behind the caller (the job's thread pwrites the rendered units);
  * bwtmi_job_write_join waits for it and returns its error */
 int bwtmi_job_write_units_async(bwtmi_job *job, const char *path, const int64_t *offsets, int write_header);
-/* final records as rows of int64: start, end, length, tier, n_copies_eval,
+/* final records (built on first use, see bwtmi_job_stage_ms; any thread) as
+ * rows of int64: start, end, length, tier, n_copies_eval,
  * max_mm, score, flags (1: composition None / entropy 0.0, 2: k-mer scan piece),
  * chrom_id and doubles: copies, mismatch_rate, confidence, percent_matches,
  * percent_indels (for tests / the Python record view) */
@@ -603,8 +604,13 @@ int64_t bwtmi_job_contig_error(const bwtmi_job *job, int32_t id, char *buf, int6
  * Every fold unit runs merge, refine, collapse and the final filter in one
  * pass (over the segments between verified cuts; a unit of several contigs, a
  * contig with Tier 3 records, or any unit under BWTMI_FOLD_CUTS=0 is one
- * segment): `merge` is that pass with its cut bits, `refine..filter` the
- * materialisation of the surviving records. */
+ * segment): `merge` is that pass with its cut bits, the gathering of its
+ * survivors included; `refine..filter` is the time spent building records from
+ * them inside postprocess -- 0 when every unit with records is one contig:
+ * the job then keeps the survivors, the writers read those, and records are
+ * built by the first call that asks for them (bwtmi_job_get_records,
+ * _get_string(s), _export; before _import, _set_records, the Tier entry
+ * points, a new contig or load). */
 int bwtmi_job_stage_ms(const bwtmi_job *job, double *out8);
 
 /* Shard layout over ranks (replaces the Pool over contigs, bwt.py:3850-3912):
