@@ -38,6 +38,10 @@ class ChainParams(C.Structure):
                 ("min_score", C.c_int32), ("min_anchors", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class AlignParams(C.Structure):
+    _fields_ = [("band", C.c_int32), ("reserved", C.c_int32 * 3), ("max_cells", C.c_int64)]
+
+
 class LibParams(C.Structure):
     _fields_ = [("min_period", C.c_int32), ("max_period", C.c_int32), ("max_short_motif", C.c_int32),
                 ("min_copies", C.c_int32), ("min_array_length", C.c_int32), ("allow_mismatches", C.c_int32),
@@ -93,6 +97,9 @@ _SIGS = {
     "bwtmi_index_map_batch": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_uint32, C.c_int64, C.c_int64,
                                         C.POINTER(ChainParams)] + [C.POINTER(C.c_void_p)] * 12 +
                               [C.POINTER(C.c_int64)] * 6),
+    "bwtmi_index_align_chains": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64,
+                                           C.POINTER(AlignParams)] + [C.POINTER(C.c_void_p)] * 9 +
+                                 [C.POINTER(C.c_int64)] * 2 + [_P]),
     "bwtmi_index_lcp_plateaus": (C.c_int, [_P, _P, C.POINTER(LibParams), C.POINTER(C.c_void_p),
                                            C.POINTER(C.c_int64)]),
     "bwtmi_index_short_imperfect": (C.c_int, [_P, _P, C.POINTER(LibParams), _P, C.c_int64, _P, C.c_int32]),

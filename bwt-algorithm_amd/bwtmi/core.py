@@ -146,6 +146,35 @@ class MapResult:
                 self.rstart[a:b], self.rend[a:b], [self.members(k) for k in range(a, b)])
 
 
+class AlignResult:
+    """Base-level alignments of BWTCore.align_chains, one per chain of the
+    MapResult it was given: `cigar_offsets` (int64[nchain + 1]) into `cigar`
+    (uint32, len << 4 | op with BAM's codes I = 1, D = 2, '=' = 7, X = 8; on
+    strand '-' in the reverse complement's order, PAF's convention); `nm` (the
+    bases in X, I and D), `n_eq` (the bases in '='), `cols` (all columns),
+    `qstart`, `qend` (int32, the original query's coordinates on both strands)
+    and `rstart`, `rend` (int64): the aligned span, from the chain's first
+    anchor to its last.  `cells_total` is the DP cells of the call (what
+    max_cells caps), `gaps` the gaps by class: (no DP, one lane, one wave)."""
+
+    __slots__ = ("cigar_offsets", "cigar", "nm", "n_eq", "cols", "qstart", "qend", "rstart", "rend", "cells_total",
+                 "gaps")
+    OPS = {1: "I", 2: "D", 7: "=", 8: "X"}
+
+    def __init__(self, cigar_offsets, cigar, nm, n_eq, cols, qstart, qend, rstart, rend, cells_total=0, gaps=(0, 0, 0)):
+        self.cigar_offsets, self.cigar, self.nm, self.n_eq, self.cols = cigar_offsets, cigar, nm, n_eq, cols
+        self.qstart, self.qend, self.rstart, self.rend = qstart, qend, rstart, rend
+        self.cells_total, self.gaps = cells_total, gaps
+
+    def __len__(self):
+        return self.cigar_offsets.size - 1
+
+    def cigar_string(self, k: int) -> str:
+        """Chain k's CIGAR as text, e.g. 40=1X145=24D74=."""
+        a, b = int(self.cigar_offsets[k]), int(self.cigar_offsets[k + 1])
+        return "".join(f"{int(v) >> 4}{self.OPS[int(v) & 15]}" for v in self.cigar[a:b])
+
+
 class BWTCore:
     BASE_TO_BITS = {"A": 0, "C": 1, "G": 2, "T": 3, "N": 0}
     BITS_TO_BASE = {0: "A", 1: "C", 2: "G", 3: "T"}
@@ -483,6 +512,63 @@ class BWTCore:
             counts = (nq + 1, n, n, n, n, n, n, n, n + 1, m, m, m)
             return MapResult(*[_lib.take(p, t, k) for p, t, k in zip(ptrs, kinds, counts)], total.value, skipped.value,
                              anchors.value, evals.value)
+        finally:
+            for p in ptrs:
+                lib().bwtmi_free(p)
+
+    def align_chains(self, queries: Sequence[Union[str, bytes]], map_result, band: Optional[int] = None,
+                     max_cells: Optional[int] = None) -> "AlignResult":
+        """Every chain of `map_result` (a MapResult of map_batch on the same
+        `queries`, or any object with its arrays: hand-made chains) aligned
+        base by base on the device: a banded edit-distance DP with traceback
+        per gap between anchors, one CIGAR per chain (include/bwtmi.h,
+        bwtmi_index_align_chains, states the contract).  band: the DP's W
+        (default 32, 0 is legal, at most 1024); max_cells: the cap on the
+        call's DP cells (default 2^30).  ValueError for chains the contract
+        refuses and for a band outside 0..1024; BwtmiError, with the count in
+        its `cells_total`, when the cells exceed max_cells."""
+        if band is not None and int(band) < 0:
+            raise ValueError("band must not be negative")
+        if max_cells is not None and int(max_cells) <= 0:
+            raise ValueError("max_cells must be positive")
+        enc = [q.encode("utf-8") if isinstance(q, str) else bytes(q) for q in queries]
+        off = np.zeros(len(enc) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(e) for e in enc]) if enc else 0
+        blob = np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8)
+        nq = off.size - 1
+        r = map_result
+        arrs = [np.ascontiguousarray(a, dtype=t) for a, t in (
+            (r.offsets, np.int64), (r.strand, np.uint8), (r.member_offsets, np.int64), (r.member_q, np.int32),
+            (r.member_r, np.int64), (r.member_len, np.int32))]
+        coff, strand, moff, mq, mr, ml = arrs
+        if coff.size != nq + 1 or moff.size != strand.size + 1 or not mq.size == mr.size == ml.size:
+            raise ValueError("the chains' arrays do not fit the queries or each other")
+        ap = _lib.AlignParams()
+        ap.band = -1 if band is None else int(band)
+        ap.max_cells = 0 if max_cells is None else int(max_cells)
+        ptrs = [C.c_void_p() for _ in range(9)]
+        nc, cells = C.c_int64(0), C.c_int64(0)
+        gaps = (C.c_int64 * 3)()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None      # noqa: E731
+        rc = lib().bwtmi_index_align_chains(self._ctx, self._h, blob.ctypes.data_as(C.c_void_p),
+                                            off.ctypes.data_as(C.c_void_p), nq, coff.ctypes.data_as(C.c_void_p),
+                                            ptr(strand), moff.ctypes.data_as(C.c_void_p), ptr(mq), ptr(mr), ptr(ml),
+                                            strand.size, mq.size, C.byref(ap), *[C.byref(p) for p in ptrs],
+                                            C.byref(nc), C.byref(cells), gaps)
+        if rc == -1:   # BWTMI_E_ARG
+            msg = lib().bwtmi_last_error()
+            raise ValueError(msg.decode(errors="replace") if msg else "bad argument")
+        try:
+            check(rc)
+        except _lib.BwtmiError as e:
+            e.cells_total = cells.value   # the count a tripped cap reports (0 for any other failure)
+            raise
+        try:
+            n = strand.size
+            kinds = (np.int64, np.uint32, np.int32, np.int32, np.int32, np.int32, np.int32, np.int64, np.int64)
+            counts = (n + 1, nc.value, n, n, n, n, n, n, n)
+            return AlignResult(*[_lib.take(p, t, k) for p, t, k in zip(ptrs, kinds, counts)], cells.value,
+                               tuple(int(v) for v in gaps))
         finally:
             for p in ptrs:
                 lib().bwtmi_free(p)

@@ -3,7 +3,7 @@ shorter they are there -- the SMEM seeds of `seeds.py` chained on the device,
 one PAF row per chain.
 
     python map.py IN.fa QUERIES [-l MIN_LEN] [--both-strands] [--long] [--max-occ N] [--max-gap N]
-                  [--bandwidth N] [--min-score N] [--min-anchors N] -o OUT.paf
+                  [--bandwidth N] [--min-score N] [--min-anchors N] [--cigar [--align-band N]] -o OUT.paf
 
 QUERIES is in the pattern-file format of `locate.py` (`SEQ` or `NAME<TAB>SEQ`
 per line).  One FM index per contig (seq + '$', built on the device, released
@@ -19,7 +19,12 @@ its anchors, `dl:i:` = (last qe - first qe) - (last re - first re) over the
 chain's anchors in the searched string's coordinates: positive when the read
 is longer than the reference there -- through both flanks of a tandem repeat,
 the tract's length difference.  Chains are per contig: each contig has its own
-index.  Not in the reference: `bwt.py` stays the drop-in, this tool stands next
+index.  With `--cigar` every chain is also aligned base by base on the device
+(BWTCore.align_chains: a banded DP per gap between anchors, `--align-band` its
+W, default 32): columns 3, 4, 8 and 9 become the aligned span (first anchor to
+last), column 10 the bases in `=`, column 11 the alignment's columns, and the
+row gains `NM:i:` and `cg:Z:` (with `=` and `X`; on strand `-` in the reverse
+complement's order) after `dl:i:`.  Not in the reference: `bwt.py` stays the drop-in, this tool stands next
 to it.
 """
 from __future__ import annotations
@@ -32,9 +37,11 @@ from typing import List, Optional, Sequence
 from .locate import parse_patterns
 
 
-def map_rows(chrom: str, tlen: int, names: Sequence[str], qlens: Sequence[int], res) -> List[str]:
+def map_rows(chrom: str, tlen: int, names: Sequence[str], qlens: Sequence[int], res, aln=None) -> List[str]:
     """PAF rows of one contig's chains (`res`: the arrays of a MapResult), in
-    the result's order: query order, then strand, then the chainer's order."""
+    the result's order: query order, then strand, then the chainer's order.
+    `aln` (the AlignResult of the same chains): the rows carry the alignment's
+    span, matches, columns, NM:i: and cg:Z: (the module's text says how)."""
     off = [int(v) for v in res.offsets]
     mo = [int(v) for v in res.member_offsets]
     rows = []
@@ -49,10 +56,16 @@ def map_rows(chrom: str, tlen: int, names: Sequence[str], qlens: Sequence[int], 
             re = [int(v) + l for v, l in zip(res.member_r[a:b], ln)]
             nmatch = ln[0] + sum(min(ln[i], qe[i] - qe[i - 1], re[i] - re[i - 1]) for i in range(1, b - a))
             dl = (qe[-1] - qe[0]) - (re[-1] - re[0])
-            qs, qend, ts, te = int(res.qstart[k]), int(res.qend[k]), int(res.rstart[k]), int(res.rend[k])
+            tags = f"s1:i:{int(res.score[k])}\tcm:i:{int(res.n_anchors[k])}\tdl:i:{dl}"
+            if aln is None:
+                qs, qend, ts, te = int(res.qstart[k]), int(res.qend[k]), int(res.rstart[k]), int(res.rend[k])
+                alen = max(qend - qs, te - ts)
+            else:
+                qs, qend, ts, te = int(aln.qstart[k]), int(aln.qend[k]), int(aln.rstart[k]), int(aln.rend[k])
+                nmatch, alen = int(aln.n_eq[k]), int(aln.cols[k])
+                tags += f"\tNM:i:{int(aln.nm[k])}\tcg:Z:{aln.cigar_string(k)}"
             rows.append(f"{names[q]}\t{m}\t{qs}\t{qend}\t{'-' if rev else '+'}\t{chrom}\t{tlen}\t{ts}\t{te}\t{nmatch}\t"
-                        f"{max(qend - qs, te - ts)}\t255\ts1:i:{int(res.score[k])}\tcm:i:{int(res.n_anchors[k])}\t"
-                        f"dl:i:{dl}\n")
+                        f"{alen}\t255\t{tags}\n")
     return rows
 
 
@@ -72,6 +85,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Largest difference between the query and reference gaps (default: 500)")
     p.add_argument("--min-score", type=int, default=None, help="Lowest chain score reported (default: 40)")
     p.add_argument("--min-anchors", type=int, default=None, help="Fewest anchors of a reported chain (default: 1)")
+    p.add_argument("--cigar", action="store_true",
+                   help="Align every chain base by base on the device: aligned span, matches, columns, NM:i: and cg:Z:")
+    p.add_argument("--align-band", type=int, default=None,
+                   help="With --cigar: the band W of the DP between anchors (default: 32, at most 1024)")
     p.add_argument("-o", "--output", required=True, help="Output PAF file")
     return p
 
@@ -96,9 +113,10 @@ def main(argv: Optional[List[str]] = None) -> int:
                 try:
                     res = core.map_batch(seqs, a.min_len, a.both_strands, a.long, a.max_occ, None, max_gap=a.max_gap,
                                          bandwidth=a.bandwidth, min_score=a.min_score, min_anchors=a.min_anchors)
+                    aln = core.align_chains(seqs, res, band=a.align_band) if a.cigar else None
                 finally:
                     core.clear()
-                out.writelines(map_rows(chrom, len(seq), names, qlens, res))
+                out.writelines(map_rows(chrom, len(seq), names, qlens, res, aln))
         os.replace(tmp, a.output)
     except (ValueError, RuntimeError, OSError) as e:   # a bad query or parameter, a tripped cap, an unreadable file
         if os.path.exists(tmp):

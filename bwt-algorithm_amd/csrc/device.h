@@ -522,4 +522,23 @@ void index_map_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *
                      bool both_strands, bool long_entry, int64_t max_occ, int64_t max_positions, const ChainParams &p,
                      MapResult &out);
 
+// ----- base-level alignment of chains (align.hip; contract in bwtmi.h)
+struct AlignParams {   // resolved, as ChainParams is
+    int32_t band = 32;
+    int64_t max_cells = int64_t{1} << 30;
+};
+struct AlignResult {
+    std::vector<int64_t> cigar_off;                        // nchain + 1
+    std::vector<uint32_t> cigar;
+    std::vector<int32_t> nm, n_eq, cols, aq_start, aq_end;   // per chain
+    std::vector<int64_t> ar_start, ar_end;
+    int64_t cells_total = 0;
+    int64_t gaps[3] = {0, 0, 0};                           // no DP, one lane, one wave
+};
+// the arrays of a MapResult (host); validates them before anything reaches the device
+void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq,
+                        const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
+                        const int32_t *mq, const int64_t *mr, const int32_t *mlen, int64_t nchain, int64_t nmember,
+                        const AlignParams &p, AlignResult &out);
+
 }  // namespace bwtmi

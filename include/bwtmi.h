@@ -489,6 +489,85 @@ int bwtmi_index_map_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, c
                           int64_t *nchain, int64_t *nmember, int64_t *positions_total, int64_t *skipped_smems,
                           int64_t *anchors, int64_t *evals);
 
+/* ------------------------------------------------------------ base-level alignment of chains
+ * What the read looks like between a chain's anchors (not in the reference): a
+ * banded edit-distance DP with traceback per inter-anchor gap on the device
+ * (align.hip), stitched into one CIGAR per chain.  Everything is in integers
+ * and in the searched string's coordinates: S = Q on strand 0, S = revcomp(Q)
+ * on strand 1 (A<->T, C<->G, every other byte unchanged, reversed, as
+ * everywhere else); T is the index text.
+ *   segments a chain's anchors in chain order are (q_i, r_i, len_i), qe_i = q_i +
+ *            len_i, re_i = r_i + len_i.  Block 0 is anchor 0 whole: len_0 columns
+ *            of '='.  For i >= 1: dq = qe_i - qe_(i-1) and dr = re_i - re_(i-1),
+ *            both > 0; t_i = min(len_i, dq, dr); gap i is a = S[qe_(i-1), qe_i -
+ *            t_i) against b = T[re_(i-1), re_i - t_i), of m = dq - t_i and n = dr -
+ *            t_i bytes; block i is t_i columns of '=' (the trimming of map.py's
+ *            nmatch).  Blocks are taken on trust: their bytes are not compared.
+ *   gap DP   delta = n - m, lo = min(0, delta) - W, hi = max(0, delta) + W.  A
+ *            cell (i, j), 0 <= i <= m, 0 <= j <= n, is in the band when lo <= j -
+ *            i <= hi.  D[0][0] = 0; any other in-band cell is the minimum of
+ *              D[i-1][j-1] + (a[i-1] != b[j-1])
+ *              D[i][j-1] + 1
+ *              D[i-1][j] + 1
+ *            over the candidates whose source cell exists and is in the band.
+ *            Bytes compare by equality.
+ *   trace    from (m, n); at each cell the first of these that reproduces
+ *            D[i][j]: the diagonal ('=' when the bytes are equal, else 'X'), left
+ *            ('D', one text byte), up ('I', one query byte).
+ *   CIGAR    of a chain: blocks and gaps in order, adjacent equal operations
+ *            merged; each a uint32 len << 4 | op with BAM's codes I = 1, D = 2,
+ *            '=' = 7, X = 8.  On strand 1 it stays in S's order (PAF's rule).
+ *   fields   per chain: nm = the bases in X, I and D; n_eq = the bases in '=';
+ *            cols = all columns; the aligned span [q_0, qe_last) x [r_0,
+ *            re_last): aq_start, aq_end in the original query's coordinates on
+ *            both strands (as qstart / qend are), ar_start, ar_end.  The span
+ *            can differ from the chain's rstart / rend, which are minima and
+ *            maxima over the anchors.
+ *   params   band = W: negative, the default 32; 0 is legal; above 1024,
+ *            BWTMI_E_ARG.  max_cells <= 0: the default 2^30.  Both defaults are
+ *            choices (a band that holds the indels of a read's gap next to a
+ *            tract difference already counted in delta; a cap of 1 GiB of
+ *            scratch), not measurements.  params = NULL: all defaults.
+ *   cap      cells(gap) = (m + 1) (|delta| + 2 W + 1) when m > 0 and n > 0, else
+ *            0; the call's count is the sum over its gaps.  Above max_cells the
+ *            call fails with BWTMI_E_NOMEM and the count in the message; nothing
+ *            is truncated.  *cells_total (may be NULL) receives the count either
+ *            way.  The device's scratch for the DP is one byte per cell of the
+ *            gaps that take a wave and at most 289 bytes per gap that takes a
+ *            lane (the classes are under `out`).
+ *   in       exactly the arrays bwtmi_index_map_batch returns (the two calls
+ *            compose without conversion; hand-made chains can be fed in):
+ *            chain_off[nq + 1] the queries' offsets into the chains, strand
+ *            [nchain], member_off[nchain + 1] into member_q, member_r, member_len
+ *            [nmember].  member_q is in the original query's coordinates; a
+ *            strand-1 chain's members come in chain order.
+ *   out      cigar_off[nchain + 1] (int64) into cigar[*ncigar] (uint32); nm, n_eq,
+ *            cols, aq_start, aq_end (int32), ar_start, ar_end (int64), one per
+ *            chain.  All nine are malloc'd (never NULL on success, nchain = 0
+ *            included; free with bwtmi_free).  gaps (may be NULL) receives three
+ *            counts: the gaps with m = 0, n = 0 or m = n = 1, which need no DP;
+ *            the other gaps with both sides <= 16, one lane each; the rest, one
+ *            wave each.
+ *   errors   BWTMI_E_ARG before anything reaches the device, every output pointer
+ *            NULL and every count 0: offsets that decrease or do not start at 0
+ *            and end at nchain / nmember; strand > 1; a chain without a member;
+ *            len < 1; a member outside its query, or r < 0, or re > the text's
+ *            n; dq <= 0 or dr <= 0 between consecutive members; a gap side above
+ *            65,535; a query of 2^28 bytes or more or a reference span of 2^30
+ *            or more (an operation's length has 28 bits, cols 31); band > 1024;
+ *            a nonzero reserved field.  nq = 0 and nchain = 0 are legal. */
+typedef struct {
+    int32_t band, reserved[3];
+    int64_t max_cells;
+} bwtmi_align_params;
+int bwtmi_index_align_chains(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                             const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
+                             const int32_t *member_q, const int64_t *member_r, const int32_t *member_len,
+                             int64_t nchain, int64_t nmember, const bwtmi_align_params *params, int64_t **cigar_off,
+                             uint32_t **cigar, int32_t **nm, int32_t **n_eq, int32_t **cols, int32_t **aq_start,
+                             int32_t **aq_end, int64_t **ar_start, int64_t **ar_end, int64_t *ncigar,
+                             int64_t *cells_total, int64_t *gaps);
+
 /* ------------------------------------------------------------ repeat job
  * Replaces the per-contig worker result handling and the post-processing of
  * TandemRepeatFinder (bwt.py:3040-3141, 3402-3944) and save_results with
