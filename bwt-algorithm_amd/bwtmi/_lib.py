@@ -42,6 +42,11 @@ class AlignParams(C.Structure):
     _fields_ = [("band", C.c_int32), ("reserved", C.c_int32 * 3), ("max_cells", C.c_int64)]
 
 
+class ExtendParams(C.Structure):
+    _fields_ = [("band", C.c_int32), ("ext_band", C.c_int32), ("match", C.c_int32), ("mismatch", C.c_int32),
+                ("gap", C.c_int32), ("xdrop", C.c_int32), ("reserved", C.c_int32 * 2), ("max_cells", C.c_int64)]
+
+
 class LibParams(C.Structure):
     _fields_ = [("min_period", C.c_int32), ("max_period", C.c_int32), ("max_short_motif", C.c_int32),
                 ("min_copies", C.c_int32), ("min_array_length", C.c_int32), ("allow_mismatches", C.c_int32),
@@ -100,6 +105,9 @@ _SIGS = {
     "bwtmi_index_align_chains": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64,
                                            C.POINTER(AlignParams)] + [C.POINTER(C.c_void_p)] * 9 +
                                  [C.POINTER(C.c_int64)] * 2 + [_P]),
+    "bwtmi_index_align_extend": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64,
+                                           C.POINTER(ExtendParams)] + [C.POINTER(C.c_void_p)] * 11 +
+                                 [C.POINTER(C.c_int64)] * 2 + [_P, C.POINTER(C.c_int64)]),
     "bwtmi_index_lcp_plateaus": (C.c_int, [_P, _P, C.POINTER(LibParams), C.POINTER(C.c_void_p),
                                            C.POINTER(C.c_int64)]),
     "bwtmi_index_short_imperfect": (C.c_int, [_P, _P, C.POINTER(LibParams), _P, C.c_int64, _P, C.c_int32]),

@@ -155,16 +155,22 @@ class AlignResult:
     `qstart`, `qend` (int32, the original query's coordinates on both strands)
     and `rstart`, `rend` (int64): the aligned span, from the chain's first
     anchor to its last.  `cells_total` is the DP cells of the call (what
-    max_cells caps), `gaps` the gaps by class: (no DP, one lane, one wave)."""
+    max_cells caps), `gaps` the gaps by class: (no DP, one lane, one wave).
+    With extend=True the CIGAR, the counts and the span include the extensions
+    past the outer anchors, `head_score` and `tail_score` (int32 per chain) are
+    their best scores and `ext_rows` the DP rows they took; all three are None
+    without extension."""
 
     __slots__ = ("cigar_offsets", "cigar", "nm", "n_eq", "cols", "qstart", "qend", "rstart", "rend", "cells_total",
-                 "gaps")
+                 "gaps", "head_score", "tail_score", "ext_rows")
     OPS = {1: "I", 2: "D", 7: "=", 8: "X"}
 
-    def __init__(self, cigar_offsets, cigar, nm, n_eq, cols, qstart, qend, rstart, rend, cells_total=0, gaps=(0, 0, 0)):
+    def __init__(self, cigar_offsets, cigar, nm, n_eq, cols, qstart, qend, rstart, rend, cells_total=0, gaps=(0, 0, 0),
+                 head_score=None, tail_score=None, ext_rows=None):
         self.cigar_offsets, self.cigar, self.nm, self.n_eq, self.cols = cigar_offsets, cigar, nm, n_eq, cols
         self.qstart, self.qend, self.rstart, self.rend = qstart, qend, rstart, rend
         self.cells_total, self.gaps = cells_total, gaps
+        self.head_score, self.tail_score, self.ext_rows = head_score, tail_score, ext_rows
 
     def __len__(self):
         return self.cigar_offsets.size - 1
@@ -517,7 +523,9 @@ class BWTCore:
                 lib().bwtmi_free(p)
 
     def align_chains(self, queries: Sequence[Union[str, bytes]], map_result, band: Optional[int] = None,
-                     max_cells: Optional[int] = None) -> "AlignResult":
+                     max_cells: Optional[int] = None, extend: bool = False, ext_band: Optional[int] = None,
+                     match: Optional[int] = None, mismatch: Optional[int] = None, gap: Optional[int] = None,
+                     xdrop: Optional[int] = None) -> "AlignResult":
         """Every chain of `map_result` (a MapResult of map_batch on the same
         `queries`, or any object with its arrays: hand-made chains) aligned
         base by base on the device: a banded edit-distance DP with traceback
@@ -526,9 +534,21 @@ class BWTCore:
         (default 32, 0 is legal, at most 1024); max_cells: the cap on the
         call's DP cells (default 2^30).  ValueError for chains the contract
         refuses and for a band outside 0..1024; BwtmiError, with the count in
-        its `cells_total`, when the cells exceed max_cells."""
+        its `cells_total`, when the cells exceed max_cells.
+        extend=True (bwtmi_index_align_extend): every chain is also extended
+        past its outer anchors towards the read's ends, a scored banded DP
+        with X-drop; ext_band its band (default 32, at most 1024), match,
+        mismatch, gap its scores (defaults 1, 3, 3; at most 64), xdrop its X
+        (default 30).  The result then carries head_score, tail_score and
+        ext_rows."""
         if band is not None and int(band) < 0:
             raise ValueError("band must not be negative")
+        ext = dict(ext_band=ext_band, match=match, mismatch=mismatch, gap=gap, xdrop=xdrop)
+        for k, v in ext.items():
+            if v is not None and not extend:
+                raise ValueError(f"{k} needs extend=True")
+            if v is not None and int(v) < 0:
+                raise ValueError(f"{k} must not be negative")
         if max_cells is not None and int(max_cells) <= 0:
             raise ValueError("max_cells must be positive")
         enc = [q.encode("utf-8") if isinstance(q, str) else bytes(q) for q in queries]
@@ -543,18 +563,21 @@ class BWTCore:
         coff, strand, moff, mq, mr, ml = arrs
         if coff.size != nq + 1 or moff.size != strand.size + 1 or not mq.size == mr.size == ml.size:
             raise ValueError("the chains' arrays do not fit the queries or each other")
-        ap = _lib.AlignParams()
+        ap = _lib.ExtendParams() if extend else _lib.AlignParams()
         ap.band = -1 if band is None else int(band)
         ap.max_cells = 0 if max_cells is None else int(max_cells)
-        ptrs = [C.c_void_p() for _ in range(9)]
-        nc, cells = C.c_int64(0), C.c_int64(0)
+        for k, v in ext.items():
+            if extend:
+                setattr(ap, k, -1 if v is None else int(v))
+        ptrs = [C.c_void_p() for _ in range(11 if extend else 9)]
+        nc, cells, rows = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         gaps = (C.c_int64 * 3)()
         ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None      # noqa: E731
-        rc = lib().bwtmi_index_align_chains(self._ctx, self._h, blob.ctypes.data_as(C.c_void_p),
-                                            off.ctypes.data_as(C.c_void_p), nq, coff.ctypes.data_as(C.c_void_p),
-                                            ptr(strand), moff.ctypes.data_as(C.c_void_p), ptr(mq), ptr(mr), ptr(ml),
-                                            strand.size, mq.size, C.byref(ap), *[C.byref(p) for p in ptrs],
-                                            C.byref(nc), C.byref(cells), gaps)
+        entry = lib().bwtmi_index_align_extend if extend else lib().bwtmi_index_align_chains
+        rc = entry(self._ctx, self._h, blob.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), nq,
+                   coff.ctypes.data_as(C.c_void_p), ptr(strand), moff.ctypes.data_as(C.c_void_p), ptr(mq), ptr(mr),
+                   ptr(ml), strand.size, mq.size, C.byref(ap), *[C.byref(p) for p in ptrs], C.byref(nc),
+                   C.byref(cells), gaps, *([C.byref(rows)] if extend else []))
         if rc == -1:   # BWTMI_E_ARG
             msg = lib().bwtmi_last_error()
             raise ValueError(msg.decode(errors="replace") if msg else "bad argument")
@@ -567,8 +590,12 @@ class BWTCore:
             n = strand.size
             kinds = (np.int64, np.uint32, np.int32, np.int32, np.int32, np.int32, np.int32, np.int64, np.int64)
             counts = (n + 1, nc.value, n, n, n, n, n, n, n)
-            return AlignResult(*[_lib.take(p, t, k) for p, t, k in zip(ptrs, kinds, counts)], cells.value,
-                               tuple(int(v) for v in gaps))
+            res = AlignResult(*[_lib.take(p, t, k) for p, t, k in zip(ptrs, kinds, counts)], cells.value,
+                              tuple(int(v) for v in gaps))
+            if extend:
+                res.head_score, res.tail_score = (_lib.take(p, np.int32, n) for p in ptrs[9:])
+                res.ext_rows = rows.value
+            return res
         finally:
             for p in ptrs:
                 lib().bwtmi_free(p)

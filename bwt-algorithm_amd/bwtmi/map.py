@@ -3,7 +3,8 @@ shorter they are there -- the SMEM seeds of `seeds.py` chained on the device,
 one PAF row per chain.
 
     python map.py IN.fa QUERIES [-l MIN_LEN] [--both-strands] [--long] [--max-occ N] [--max-gap N]
-                  [--bandwidth N] [--min-score N] [--min-anchors N] [--cigar [--align-band N]] -o OUT.paf
+                  [--bandwidth N] [--min-score N] [--min-anchors N] [--cigar [--align-band N]]
+                  [--extend [--xdrop N] [--ext-band N]] -o OUT.paf
 
 QUERIES is in the pattern-file format of `locate.py` (`SEQ` or `NAME<TAB>SEQ`
 per line).  One FM index per contig (seq + '$', built on the device, released
@@ -24,7 +25,11 @@ index.  With `--cigar` every chain is also aligned base by base on the device
 W, default 32): columns 3, 4, 8 and 9 become the aligned span (first anchor to
 last), column 10 the bases in `=`, column 11 the alignment's columns, and the
 row gains `NM:i:` and `cg:Z:` (with `=` and `X`; on strand `-` in the reverse
-complement's order) after `dl:i:`.  Not in the reference: `bwt.py` stays the drop-in, this tool stands next
+complement's order) after `dl:i:`.  With `--extend` (implies `--cigar`) every
+alignment is also extended past its outer anchors towards the read's ends, a
+scored banded DP with X-drop (`--xdrop`, default 30; `--ext-band`, default 32):
+the same columns and tags, with the extended span, matches, columns, `NM:i:`
+and `cg:Z:`.  Not in the reference: `bwt.py` stays the drop-in, this tool stands next
 to it.
 """
 from __future__ import annotations
@@ -89,6 +94,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Align every chain base by base on the device: aligned span, matches, columns, NM:i: and cg:Z:")
     p.add_argument("--align-band", type=int, default=None,
                    help="With --cigar: the band W of the DP between anchors (default: 32, at most 1024)")
+    p.add_argument("--extend", action="store_true",
+                   help="Extend every alignment past its outer anchors towards the read's ends (implies --cigar)")
+    p.add_argument("--xdrop", type=int, default=None,
+                   help="With --extend: stop once a row's best score lies this far below the best (default: 30)")
+    p.add_argument("--ext-band", type=int, default=None,
+                   help="With --extend: the band of the extension DP (default: 32, at most 1024)")
     p.add_argument("-o", "--output", required=True, help="Output PAF file")
     return p
 
@@ -113,7 +124,11 @@ def main(argv: Optional[List[str]] = None) -> int:
                 try:
                     res = core.map_batch(seqs, a.min_len, a.both_strands, a.long, a.max_occ, None, max_gap=a.max_gap,
                                          bandwidth=a.bandwidth, min_score=a.min_score, min_anchors=a.min_anchors)
-                    aln = core.align_chains(seqs, res, band=a.align_band) if a.cigar else None
+                    if a.extend:
+                        aln = core.align_chains(seqs, res, band=a.align_band, extend=True, ext_band=a.ext_band,
+                                                xdrop=a.xdrop)
+                    else:
+                        aln = core.align_chains(seqs, res, band=a.align_band) if a.cigar else None
                 finally:
                     core.clear()
                 out.writelines(map_rows(chrom, len(seq), names, qlens, res, aln))

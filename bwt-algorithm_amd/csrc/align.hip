@@ -37,6 +37,18 @@
 // from the gap's descriptor at a wave-uniform address: no lane leaves a loop on a
 // cross-lane value (Guard).  The other kernels have no cross-lane
 // operation at all.
+//
+// bwtmi_index_align_extend adds, per chain, a head and a tail: a scored banded DP
+// with X-drop from each outer anchor towards the read's end.
+//   k_extend_score  one wave per extension, score only: the best cell and the
+//                   rows computed; the X-drop exit is on a scalar
+//   host            reads the best cells: the cap on the whole call's cells, the
+//                   spans, and each extension's offsets into the directions (one
+//                   byte per cell of the rows up to the best cell's) and the
+//                   operations
+//   k_extend_dirs   the same rows again, up to the best cell's, directions stored
+//   k_extend_trace  one lane per extension, from the best cell to (0, 0)
+//   k_align_stitch  takes the head's and the tail's operations as two more runs
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -237,13 +249,194 @@ __global__ __launch_bounds__(256) void k_align_trace(const AlignGap *__restrict_
     opcnt[t] = cnt;
 }
 
+// ---- extension past the outer anchors (contract: include/bwtmi.h, bwtmi_index_align_extend)
+// Extension 2k is chain k's head, 2k + 1 its tail.  A head is the tail rule on
+// the reversed strings, so a descriptor says which way its bytes run.
+struct AlignExt {
+    int64_t qa;      // a[i] is the query blob's byte qa + i (flags bit 1: qa - i), complemented on flags bit 0
+    int64_t rb;      // b[j] = T[rb + j] (flags bit 2: T[rb - j])
+    int32_t m, n;    // m = 0 or n = 0: no extension
+    int32_t flags;   // bit 0 complement, bit 1 the query bytes descend, bit 2 the text bytes descend (a head)
+    int32_t pad;
+};
+static_assert(sizeof(AlignExt) == 32, "AlignExt layout");
+struct ExtBest {     // k_extend_score's answer
+    int32_t bi, bj, score, rows;
+};
+struct ExtPlan {     // the host's, from the best cells
+    int64_t dir;     // its first direction byte: (bi + 1) (2 We + 1) bytes by (i, c); row 0 is not stored
+    int64_t ops;     // its region of bi + bj operations
+};
+struct ExtScore {
+    int32_t A, B, G, X, We;
+};
+constexpr int32_t kExtNeg = -(1 << 29);      // no cell: below every score (>= -2^20 - 4 * 64 * 1024), and 2 * kExtNeg fits
+
+__device__ __forceinline__ uint8_t ext_a(const uint8_t *__restrict__ qs, const AlignExt &e, int32_t i) {
+    const uint8_t ch = qs[(e.flags & 2) ? e.qa - i : e.qa + i];
+    return (e.flags & 1) ? align_comp(ch) : ch;
+}
+__device__ __forceinline__ uint8_t ext_b(const uint8_t *__restrict__ text, const AlignExt &e, int32_t j) {
+    return text[(e.flags & 4) ? e.rb - j : e.rb + j];
+}
+
+// Rows 1 .. R of one extension, on one wave: row i over the band's columns c =
+// j - i + We, a lane owns c, c + 64, ...  rows: two rows of 2 We + 2 ints in LDS
+// (entry 2 We + 1 is a sentinel that stays kExtNeg); a cell outside the matrix
+// holds kExtNeg, so a candidate whose source does not exist never reproduces a
+// score.  t[c] = max(prev[c] + s, prev[c + 1] - G) needs no neighbour of the new
+// row; the horizontal candidate is then H[c] = -G c + prefixmax(t[c'] + G c'):
+// k_align_wave's scan and chunk carry with max for min.  Both bounds of a row
+// fall by at most one per row, so (as there) the chunks up to c_hi + 2 rewrite
+// all that the row written two rows ago left.
+// kStore = false, the score pass: R = every row that has a cell; the row's
+//   maximum and its smallest column are one wave reduction of H * 4096 + (4095 -
+//   c), taken as scalars (readfirstlane): the best cell, the row count and the
+//   X-drop exit are wave-uniform (Guard).  Writes *best.
+// kStore = true, the direction pass: R = the best cell's row, no exit; one byte
+//   per cell with the gap DP's codes and preference.
+template <bool kStore>
+__device__ __forceinline__ void extend_rows(int32_t *rows, const AlignExt &e, const uint8_t *__restrict__ qs,
+                                            const uint8_t *__restrict__ text, const ExtScore s, int32_t R,
+                                            uint8_t *__restrict__ d, ExtBest *__restrict__ out, int lane) {
+    const int32_t We = s.We, Wb = 2 * We + 1, stride = Wb + 1, m = e.m, n = e.n;
+    for (int32_t c = lane; c <= Wb; c += 64) {
+        const int32_t j = c - We;
+        rows[c] = (c < Wb && j >= 0 && j <= n) ? -s.G * j : kExtNeg;   // row 0: H[0][j] = -G j
+        rows[stride + c] = kExtNeg;
+    }
+    __syncthreads();
+    int32_t best = 0, bi = 0, bj = 0, nrows = 0;
+    uint32_t aa = 0;   // a[i - 1 + lane] of the 64 rows from i: one load per 64 rows, one readlane per row
+    for (int32_t i = 1; i <= R; ++i) {
+        if (((i - 1) & 63) == 0) aa = i - 1 + lane < m ? ext_a(qs, e, i - 1 + lane) : 0u;
+        const uint32_t ai = (uint32_t)__builtin_amdgcn_readlane((int)aa, (i - 1) & 63);
+        const int32_t *prev = rows + ((i - 1) & 1) * stride;
+        int32_t *cur = rows + (i & 1) * stride;
+        const int32_t c_lo = max(0, We - i), c_hi = min(Wb - 1, n - i + We);
+        const int32_t c_end = min(Wb - 1, c_hi + 2);
+        int32_t carry = kExtNeg;
+        long long key = INT64_MIN;
+        for (int32_t k = c_lo >> 6; k <= c_end >> 6; ++k) {
+            const int32_t c = (k << 6) + lane;
+            const int32_t j = i + c - We;
+            const bool valid = c >= c_lo && c <= c_hi;
+            const int32_t p0 = prev[min(c, Wb)], p1 = prev[min(c + 1, Wb)];
+            const bool eq = valid && j >= 1 && ai == (uint32_t)ext_b(text, e, j - 1);
+            const int32_t td = j >= 1 ? p0 + (eq ? s.A : -s.B) : kExtNeg;
+            int32_t v = (valid ? max(td, p1 - s.G) : kExtNeg) + s.G * c;
+#pragma unroll
+            for (int sh = 1; sh < 64; sh <<= 1) {   // inclusive prefix-max over the wave
+                const int32_t o = __shfl_up(v, sh, 64);
+                if (lane >= sh) v = max(v, o);
+            }
+            int32_t ex = __shfl_up(v, 1, 64);
+            if (lane == 0) ex = kExtNeg;
+            ex = max(ex, carry);
+            v = max(v, carry);
+            carry = __shfl(v, 63, 64);
+            const int32_t H = v - s.G * c;   // ex - G c = H[i][j - 1] - G
+            if (valid) {
+                cur[c] = H;
+                if (kStore) d[(int64_t)i * Wb + c] = (uint8_t)(td == H ? (eq ? 0 : 1) : ex - s.G * c == H ? 2 : 3);
+                else key = max(key, (long long)H * 4096 + (4095 - c));
+            } else if (c < Wb) {
+                cur[c] = kExtNeg;
+            }
+        }
+        if (!kStore) {
+#pragma unroll
+            for (int sh = 1; sh < 64; sh <<= 1) key = max(key, __shfl_xor(key, sh, 64));
+            const long long rk = (long long)__builtin_amdgcn_readfirstlane((int)(key >> 32)) << 32 |
+                                 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)key);
+            const int32_t rowmax = (int32_t)(rk >> 12);   // floor: the low 12 bits are 4095 - c >= 0
+            nrows = i;
+            if (rowmax > best) {   // strictly: ties keep the smaller i, and within the row the key kept the smaller j
+                best = rowmax;
+                bi = i;
+                bj = i + (4095 - (int32_t)(rk & 4095)) - We;
+            }
+            if (best - rowmax > s.X) break;   // a scalar
+        }
+        __syncthreads();   // one wave: the row's stores before the next row's loads
+    }
+    if (!kStore && lane == 0) *out = ExtBest{bi, bj, best, nrows};
+}
+
+// One workgroup of one wave per extension: its best cell and its rows.
+__global__ __launch_bounds__(64) void k_extend_score(const AlignExt *__restrict__ ext,
+                                                     const uint8_t *__restrict__ qs,
+                                                     const uint8_t *__restrict__ text, const ExtScore s,
+                                                     ExtBest *__restrict__ best) {
+    extern __shared__ int32_t lds[];   // the launch's 2 (2 We + 2) ints: 528 bytes at We = 32, 16 KiB at 1024
+    const AlignExt e = ext[blockIdx.x];
+    const int lane = (int)threadIdx.x;
+    if (e.m == 0 || e.n == 0) {
+        if (lane == 0) best[blockIdx.x] = ExtBest{0, 0, 0, 0};
+        return;
+    }
+    extend_rows<false>(lds, e, qs, text, s, min(e.m, e.n + s.We), nullptr, best + blockIdx.x, lane);
+}
+
+// One workgroup of one wave per extension whose best cell is not (0, 0): the
+// directions of the rows up to the best cell's.
+__global__ __launch_bounds__(64) void k_extend_dirs(const AlignExt *__restrict__ ext,
+                                                    const uint32_t *__restrict__ list,
+                                                    const uint8_t *__restrict__ qs,
+                                                    const uint8_t *__restrict__ text, const ExtScore s,
+                                                    const ExtBest *__restrict__ best,
+                                                    const ExtPlan *__restrict__ plan, uint8_t *__restrict__ dir) {
+    extern __shared__ int32_t lds[];   // the launch's 2 (2 We + 2) ints: 528 bytes at We = 32, 16 KiB at 1024
+    const uint32_t x = list[blockIdx.x];
+    extend_rows<true>(lds, ext[x], qs, text, s, best[x].bi, dir + plan[x].dir, nullptr, (int)threadIdx.x);
+}
+
+// One lane per listed extension walks from its best cell to (0, 0), at most bi +
+// bj dependent byte loads, and writes run-length operations forwards from the
+// start of its region: a head's are then in the CIGAR's order (the walk reverses
+// the reversed strings' alignment), a tail's in reverse (k_align_stitch reads
+// them backwards).  ecnt = how many; an extension not listed keeps its 0.
+__global__ __launch_bounds__(256) void k_extend_trace(const uint32_t *__restrict__ list, int64_t nlist, int32_t We,
+                                                      const ExtBest *__restrict__ best,
+                                                      const ExtPlan *__restrict__ plan,
+                                                      const uint8_t *__restrict__ dir, uint32_t *__restrict__ eops,
+                                                      uint32_t *__restrict__ ecnt) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nlist) return;
+    const uint32_t x = list[t];
+    const int32_t Wb = 2 * We + 1;
+    const uint8_t *d = dir + plan[x].dir;
+    uint32_t *o = eops + plan[x].ops;
+    int32_t i = best[x].bi, j = best[x].bj;
+    uint32_t cur = 0, len = 0, cnt = 0;
+    while (i > 0 || j > 0) {   // every step lowers i or j: at most bi + bj steps
+        const uint32_t code = i == 0 ? 2u : d[(int64_t)i * Wb + (j - i + We)];
+        const uint32_t op = code == 0 ? 7u : code == 1 ? 8u : code == 2 ? 2u : 1u;
+        if (code != 2) --i;
+        if (code != 3) --j;
+        if (op == cur) {
+            ++len;
+        } else {
+            if (len) o[cnt++] = len << 4 | cur;
+            cur = op;
+            len = 1;
+        }
+    }
+    if (len) o[cnt++] = len << 4 | cur;
+    ecnt[x] = cnt;
+}
+
 // One lane per chain.  cigar == nullptr: count the merged operations into nops
-// and sum nm, n_eq, cols; else write them at cigar + cig_off[chain].
+// and sum nm, n_eq, cols; else write them at cigar + cig_off[chain].  ecnt !=
+// nullptr: the chain's head operations go in front and its tail's behind.
 __global__ __launch_bounds__(64) void k_align_stitch(const int64_t *__restrict__ member_off, int64_t nchain,
                                                      const int32_t *__restrict__ blk,
                                                      const AlignGap *__restrict__ gaps,
                                                      const uint32_t *__restrict__ ops,
                                                      const uint32_t *__restrict__ opcnt,
+                                                     const ExtPlan *__restrict__ plan,
+                                                     const uint32_t *__restrict__ eops,
+                                                     const uint32_t *__restrict__ ecnt,
                                                      const uint32_t *__restrict__ cig_off, uint32_t *__restrict__ cigar,
                                                      uint32_t *__restrict__ nops, int32_t *__restrict__ nm,
                                                      int32_t *__restrict__ n_eq, int32_t *__restrict__ cols) {
@@ -251,8 +444,9 @@ __global__ __launch_bounds__(64) void k_align_stitch(const int64_t *__restrict__
     if (k >= nchain) return;
     const int64_t a = member_off[k], b = member_off[k + 1];
     uint32_t *out = cigar ? cigar + cig_off[k] : nullptr;
-    uint32_t cnt = 0, cur = 7u, len = (uint32_t)blk[a], s_eq = 0, s_nm = 0;
+    uint32_t cnt = 0, cur = 7u, len = 0, s_eq = 0, s_nm = 0;   // len = 0: nothing to flush yet
     auto flush = [&] {
+        if (len == 0) return;
         if (out) out[cnt] = len << 4 | cur;
         ++cnt;
         if (cur == 7u) s_eq += len;
@@ -267,11 +461,22 @@ __global__ __launch_bounds__(64) void k_align_stitch(const int64_t *__restrict__
             len = l;
         }
     };
+    if (ecnt) {
+        const uint32_t c = ecnt[2 * k];
+        const uint32_t *o = eops + plan[2 * k].ops;
+        for (uint32_t x = 0; x < c; ++x) put(o[x] & 15u, o[x] >> 4);
+    }
+    put(7u, (uint32_t)blk[a]);
     for (int64_t t = a + 1; t < b; ++t) {
         const uint32_t c = opcnt[t];
         const uint32_t *o = ops + gaps[t].ops_end - c;
         for (uint32_t x = 0; x < c; ++x) put(o[x] & 15u, o[x] >> 4);
         put(7u, (uint32_t)blk[t]);
+    }
+    if (ecnt) {
+        const uint32_t c = ecnt[2 * k + 1];
+        const uint32_t *o = eops + plan[2 * k + 1].ops;
+        for (uint32_t x = c; x-- > 0;) put(o[x] & 15u, o[x] >> 4);
     }
     flush();
     if (!out) {
@@ -294,18 +499,37 @@ struct AlignArena {
     template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
 };
 
-}  // namespace
+void align_fail_cells(AlignResult &out, int64_t cells, int64_t max_cells) {
+    out.aq_start.clear();
+    out.aq_end.clear();
+    out.ar_start.clear();
+    out.ar_end.clear();
+    fail(BWTMI_E_NOMEM, "align: %lld DP cells exceed max_cells %lld", (long long)cells, (long long)max_cells);
+}
 
-void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq,
-                        const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
-                        const int32_t *mq, const int64_t *mr, const int32_t *mlen, int64_t nchain, int64_t nmember,
-                        const AlignParams &p, AlignResult &out) {
+// Both entries: ep == nullptr is bwtmi_index_align_chains, whose launches and
+// arrays the extension leaves as they are.
+void align_run(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq, const int64_t *chain_off,
+               const uint8_t *strand, const int64_t *member_off, const int32_t *mq, const int64_t *mr,
+               const int32_t *mlen, int64_t nchain, int64_t nmember, const AlignParams &p, const ExtendParams *ep,
+               AlignResult &out) {
     out = AlignResult{};
     // ---- validation and the descriptors: nothing reaches the device before the last check
     if (nq < 0 || nchain < 0 || nmember < 0 || !off || !chain_off || !member_off)
         fail(BWTMI_E_ARG, "align: negative count or null offsets");
     if ((nchain > 0 && !strand) || (nmember > 0 && !(mq && mr && mlen))) fail(BWTMI_E_ARG, "align: null chain array");
     if (p.band < 0 || p.band > 1024) fail(BWTMI_E_ARG, "align: band %d outside 0..1024", (int)p.band);
+    if (ep) {
+        if (ep->ext_band < 0 || ep->ext_band > 1024)
+            fail(BWTMI_E_ARG, "align: ext_band %d outside 0..1024", (int)ep->ext_band);
+        if (ep->match < 1 || ep->match > 64) fail(BWTMI_E_ARG, "align: match %d outside 1..64", (int)ep->match);
+        if (ep->mismatch < 0 || ep->mismatch > 64)
+            fail(BWTMI_E_ARG, "align: mismatch %d outside 0..64", (int)ep->mismatch);
+        if (ep->gap < 1 || ep->gap > 64) fail(BWTMI_E_ARG, "align: gap %d outside 1..64", (int)ep->gap);
+        if (ep->xdrop < 0 || ep->xdrop > (1 << 20)) fail(BWTMI_E_ARG, "align: xdrop %d outside 0..2^20", (int)ep->xdrop);
+        if (nchain >= (int64_t{1} << 30))
+            fail(BWTMI_E_NOMEM, "align: %lld chains have 2^31 extensions and more", (long long)nchain);
+    }
     if (nchain >= (int64_t{1} << 31) || nmember >= (int64_t{1} << 31))
         fail(BWTMI_E_NOMEM, "align: %lld chains of %lld members exceed the 2^31 the aligner indexes", (long long)nchain,
              (long long)nmember);
@@ -325,6 +549,8 @@ void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_
     std::vector<AlignGap> gaps(M);
     std::vector<int32_t> blk(M);
     std::vector<uint32_t> small, wave;
+    std::vector<AlignExt> ext(ep ? 2 * C : 0);
+    const int32_t We = ep ? ep->ext_band : 0;
     out.aq_start.resize(C);
     out.aq_end.resize(C);
     out.ar_start.resize(C);
@@ -413,17 +639,21 @@ void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_
             out.ar_end[(size_t)k] = re_prev;
             out.aq_start[(size_t)k] = (int32_t)(rev ? qlen - qe_prev : sq0);
             out.aq_end[(size_t)k] = (int32_t)(rev ? qlen - sq0 : qe_prev);
+            if (ep) {
+                if (qlen * ep->match >= (int64_t{1} << 30))
+                    fail(BWTMI_E_ARG, "align: query %lld of %lld bytes at match %d: a score of 2^30 and more",
+                         (long long)qi, (long long)qlen, (int)ep->match);
+                const int64_t base = off[qi] - q0, r0 = out.ar_start[(size_t)k];
+                const int64_t hm = sq0, tm = qlen - qe_prev;
+                ext[2 * (size_t)k] = AlignExt{base + (rev ? qlen - sq0 : sq0 - 1), r0 - 1, (int32_t)hm,
+                                              (int32_t)std::min(r0, hm + We), (rev ? 1 : 2) | 4, 0};
+                ext[2 * (size_t)k + 1] = AlignExt{base + (rev ? qlen - 1 - qe_prev : qe_prev), re_prev, (int32_t)tm,
+                                                  (int32_t)std::min(tn - re_prev, tm + We), rev ? 3 : 0, 0};
+            }
         }
     }
     out.cells_total = cells;
-    if (cells > p.max_cells) {
-        const long long total = (long long)cells;
-        out.aq_start.clear();
-        out.aq_end.clear();
-        out.ar_start.clear();
-        out.ar_end.clear();
-        fail(BWTMI_E_NOMEM, "align: %lld DP cells exceed max_cells %lld", total, (long long)p.max_cells);
-    }
+    if (cells > p.max_cells) align_fail_cells(out, cells, p.max_cells);
     out.cigar_off.assign(C + 1, 0);
     if (nchain == 0) return;
 
@@ -435,6 +665,9 @@ void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_
     const size_t o_opcnt = ar.take(M * 4), o_ops = ar.take((size_t)ops_total * 4 + 4);
     const size_t o_nops = ar.take((C + 1) * 4), o_coff = ar.take((C + 1) * 4);
     const size_t o_nm = ar.take(C * 4), o_neq = ar.take(C * 4), o_cols = ar.take(C * 4);
+    const size_t E = ext.size();   // 2 C, or 0 without extension
+    const size_t o_ext = ar.take(E * sizeof(AlignExt)), o_best = ar.take(E * sizeof(ExtBest));
+    const size_t o_plan = ar.take(E * sizeof(ExtPlan)), o_elist = ar.take(E * 4 + 4), o_ecnt = ar.take(E * 4);
     c.slot[S_IDX0].ensure(ar.used);
     c.slot[S_IDX2].ensure((size_t)dir_bytes + 1);
     c.slot[S_IDX3].ensure((size_t)row_ints * 4 + 4);
@@ -447,6 +680,10 @@ void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_
     uint32_t *d_ops = ar.at<uint32_t>(o_ops), *d_nops = ar.at<uint32_t>(o_nops), *d_coff = ar.at<uint32_t>(o_coff);
     int32_t *d_nm = ar.at<int32_t>(o_nm), *d_neq = ar.at<int32_t>(o_neq), *d_cols = ar.at<int32_t>(o_cols);
     const uint8_t *d_text = index_text_device(ix);
+    AlignExt *d_ext = ar.at<AlignExt>(o_ext);
+    ExtBest *d_best = ar.at<ExtBest>(o_best);
+    ExtPlan *d_plan = ar.at<ExtPlan>(o_plan);
+    uint32_t *d_elist = ar.at<uint32_t>(o_elist), *d_ecnt = ar.at<uint32_t>(o_ecnt);
 
     hipStream_t st = c.stream;
     // timed like a kernel (statistics name align_upload): what the chains' way back up costs
@@ -457,8 +694,18 @@ void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_
     HIPCHECK(hipMemcpyAsync(d_moff, member_off, (C + 1) * 8, hipMemcpyHostToDevice, st));
     if (!small.empty()) HIPCHECK(hipMemcpyAsync(d_small, small.data(), small.size() * 4, hipMemcpyHostToDevice, st));
     if (!wave.empty()) HIPCHECK(hipMemcpyAsync(d_wave, wave.data(), wave.size() * 4, hipMemcpyHostToDevice, st));
+    if (E) HIPCHECK(hipMemcpyAsync(d_ext, ext.data(), E * sizeof(AlignExt), hipMemcpyHostToDevice, st));
     c.kend();
     HIPCHECK(hipMemsetAsync(d_nops + C, 0, 4, st));
+
+    // ---- the extensions' score pass goes first: the host plans the second pass behind the gaps' kernels
+    const size_t ext_lds = 2 * (2 * (size_t)We + 2) * sizeof(int32_t);
+    const ExtScore es{ep ? ep->match : 0, ep ? ep->mismatch : 0, ep ? ep->gap : 0, ep ? ep->xdrop : 0, We};
+    if (ep) {
+        KLAUNCH("k_extend_score", (double)E * (sizeof(AlignExt) + sizeof(ExtBest)), k_extend_score, dim3((unsigned)E),
+                dim3(64), ext_lds, st, d_ext, d_qs, d_text, es, d_best);
+        HIPCHECK(hipGetLastError());
+    }
 
     // ---- the gaps: forward passes by class, then every member's traceback
     if (!small.empty()) {
@@ -476,23 +723,95 @@ void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_
             dim3(256), 0, st, d_gaps, nmember, d_qs, d_text, W, d_dir, d_ops, d_opcnt);
     HIPCHECK(hipGetLastError());
 
+    // ---- the extensions: best cells down, the cap, the plan up, directions, traceback
+    const ExtPlan *s_plan = nullptr;     // what k_align_stitch gets: nothing without extension
+    const uint32_t *s_eops = nullptr, *s_ecnt = nullptr;
+    int64_t eops_total = 0;
+    std::vector<ExtPlan> plan(E);
+    std::vector<uint32_t> elist;
+    if (ep) {
+        ExtBest *hb = c.mailbox<ExtBest>(E);
+        HIPCHECK(hipMemcpyAsync(hb, d_best, E * sizeof(ExtBest), hipMemcpyDeviceToHost, st));
+        scan_wait(st);   // (the gaps' kernels are done too: their directions' slot is free)
+        const int64_t Wb = 2 * (int64_t)We + 1;
+        int64_t edir = 0, ecells = 0;
+        out.head_score.resize(C);
+        out.tail_score.resize(C);
+        for (size_t x = 0; x < E; ++x) {
+            const ExtBest b = hb[x];
+            const AlignExt &e = ext[x];
+            if (b.bi < 0 || b.bi > e.m || b.bj < 0 || b.bj > e.n || b.rows < b.bi || (b.bi == 0 && b.bj != 0))
+                fail(BWTMI_E_STATE, "align: extension %lld ends at (%d, %d) of %d x %d", (long long)x, (int)b.bi,
+                     (int)b.bj, (int)e.m, (int)e.n);
+            plan[x] = ExtPlan{edir, eops_total};
+            out.ext_rows += b.rows;
+            if (e.m > 0 && e.n > 0) {
+                const int64_t ce = ((int64_t)b.bi + 1) * Wb;
+                ecells = ecells > INT64_MAX - ce ? INT64_MAX : ecells + ce;
+            }
+            if (b.bi > 0) {
+                elist.push_back((uint32_t)x);
+                edir += ((int64_t)b.bi + 1) * Wb;
+                eops_total += (int64_t)b.bi + b.bj;
+            }
+            const size_t k = x >> 1;
+            const bool rev = strand[k] != 0;
+            if (x & 1) {   // a tail lengthens the searched string's end, a head its start
+                out.tail_score[k] = b.score;
+                (rev ? out.aq_start[k] : out.aq_end[k]) += rev ? -b.bi : b.bi;
+                out.ar_end[k] += b.bj;
+            } else {
+                out.head_score[k] = b.score;
+                (rev ? out.aq_end[k] : out.aq_start[k]) += rev ? b.bi : -b.bi;
+                out.ar_start[k] -= b.bj;
+            }
+        }
+        cells = cells > INT64_MAX - ecells ? INT64_MAX : cells + ecells;
+        out.cells_total = cells;
+        if (cells > p.max_cells) {
+            out.head_score.clear();
+            out.tail_score.clear();
+            out.cigar_off.clear();
+            align_fail_cells(out, cells, p.max_cells);
+        }
+        c.slot[S_IDX2].ensure((size_t)edir + 1);   // (<= the extensions' cells)
+        c.slot[S_IDX4].ensure((size_t)eops_total * 4 + 4);
+        uint8_t *d_edir = c.slot[S_IDX2].as<uint8_t>();
+        uint32_t *d_eops = c.slot[S_IDX4].as<uint32_t>();
+        HIPCHECK(hipMemcpyAsync(d_plan, plan.data(), E * sizeof(ExtPlan), hipMemcpyHostToDevice, st));
+        HIPCHECK(hipMemsetAsync(d_ecnt, 0, E * 4, st));
+        if (!elist.empty()) {
+            const int64_t nl = (int64_t)elist.size();
+            HIPCHECK(hipMemcpyAsync(d_elist, elist.data(), elist.size() * 4, hipMemcpyHostToDevice, st));
+            KLAUNCH("k_extend_dirs", (double)edir, k_extend_dirs, dim3((unsigned)nl), dim3(64), ext_lds, st, d_ext, d_elist, d_qs,
+                    d_text, es, d_best, d_plan, d_edir);
+            HIPCHECK(hipGetLastError());
+            KLAUNCH("k_extend_trace", (double)nl * 36.0 + (double)eops_total * 4.0, k_extend_trace, dim3(blocks(nl)),
+                    dim3(256), 0, st, d_elist, nl, We, d_best, d_plan, d_edir, d_eops, d_ecnt);
+            HIPCHECK(hipGetLastError());
+        }
+        s_plan = d_plan;
+        s_eops = d_eops;
+        s_ecnt = d_ecnt;
+    }
+
     // ---- the chains: count, scan, write
     KLAUNCH("k_align_stitch", (double)nmember * 12.0 + (double)ops_total * 4.0, k_align_stitch, dim3(blocks(nchain, 64)),
-            dim3(64), 0, st, d_moff, nchain, d_blk, d_gaps, d_ops, d_opcnt, (const uint32_t *)nullptr,
-            (uint32_t *)nullptr, d_nops, d_nm, d_neq, d_cols);
+            dim3(64), 0, st, d_moff, nchain, d_blk, d_gaps, d_ops, d_opcnt, s_plan, s_eops, s_ecnt,
+            (const uint32_t *)nullptr, (uint32_t *)nullptr, d_nops, d_nm, d_neq, d_cols);
     HIPCHECK(hipGetLastError());
     exclusive_scan<uint32_t>(c, d_nops, d_coff, nchain + 1);
     uint32_t *mb = c.mailbox<uint32_t>(1);
     HIPCHECK(hipMemcpyAsync(mb, d_coff + C, 4, hipMemcpyDeviceToHost, st));
     scan_wait(st);   // (the uploads above read pageable arrays: they are done too)
     const int64_t ncigar = mb[0];
-    if (ncigar < nchain || ncigar > ops_total + nmember)
+    if (ncigar < nchain || ncigar > ops_total + nmember + eops_total)
         fail(BWTMI_E_STATE, "align: %lld operations out of %lld chains", (long long)ncigar, (long long)nchain);
     c.slot[S_IDX1].ensure((size_t)ncigar * 4);
     uint32_t *d_cigar = c.slot[S_IDX1].as<uint32_t>();
     KLAUNCH("k_align_stitch", (double)nmember * 12.0 + (double)ops_total * 4.0 + (double)ncigar * 4.0, k_align_stitch,
-            dim3(blocks(nchain, 64)), dim3(64), 0, st, d_moff, nchain, d_blk, d_gaps, d_ops, d_opcnt,
-            (const uint32_t *)d_coff, d_cigar, d_nops, d_nm, d_neq, d_cols);
+            dim3(blocks(nchain, 64)), dim3(64), 0, st, d_moff, nchain, d_blk, d_gaps, d_ops, d_opcnt, s_plan, s_eops,
+            s_ecnt, (const uint32_t *)d_coff, d_cigar, d_nops, d_nm, d_neq, d_cols);
     HIPCHECK(hipGetLastError());
 
     std::vector<uint32_t> coff(C + 1);
@@ -507,6 +826,22 @@ void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_
     HIPCHECK(hipMemcpyAsync(out.cigar.data(), d_cigar, (size_t)ncigar * 4, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     out.cigar_off.assign(coff.begin(), coff.end());
+}
+
+}  // namespace
+
+void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq,
+                        const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
+                        const int32_t *mq, const int64_t *mr, const int32_t *mlen, int64_t nchain, int64_t nmember,
+                        const AlignParams &p, AlignResult &out) {
+    align_run(c, ix, qs, off, nq, chain_off, strand, member_off, mq, mr, mlen, nchain, nmember, p, nullptr, out);
+}
+
+void index_align_extend(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq,
+                        const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
+                        const int32_t *mq, const int64_t *mr, const int32_t *mlen, int64_t nchain, int64_t nmember,
+                        const AlignParams &p, const ExtendParams &e, AlignResult &out) {
+    align_run(c, ix, qs, off, nq, chain_off, strand, member_off, mq, mr, mlen, nchain, nmember, p, &e, out);
 }
 
 }  // namespace bwtmi

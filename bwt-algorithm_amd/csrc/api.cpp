@@ -933,6 +933,63 @@ int bwtmi_index_align_chains(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs
     });
 }
 
+int bwtmi_index_align_extend(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                             const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
+                             const int32_t *member_q, const int64_t *member_r, const int32_t *member_len,
+                             int64_t nchain, int64_t nmember, const bwtmi_extend_params *params, int64_t **cigar_off,
+                             uint32_t **cigar, int32_t **nm, int32_t **n_eq, int32_t **cols, int32_t **aq_start,
+                             int32_t **aq_end, int64_t **ar_start, int64_t **ar_end, int32_t **head_score,
+                             int32_t **tail_score, int64_t *ncigar, int64_t *cells_total, int64_t *gaps,
+                             int64_t *ext_rows) {
+    return guard([&] {
+        CHECK_ARG(ctx && idx && cigar_off && cigar && nm && n_eq && cols && aq_start && aq_end && ar_start && ar_end &&
+                      head_score && tail_score && ncigar,
+                  "bad argument");
+        *cigar_off = *ar_start = *ar_end = nullptr;
+        *cigar = nullptr;
+        *nm = *n_eq = *cols = *aq_start = *aq_end = *head_score = *tail_score = nullptr;
+        *ncigar = 0;
+        if (cells_total) *cells_total = 0;
+        if (gaps) gaps[0] = gaps[1] = gaps[2] = 0;
+        if (ext_rows) *ext_rows = 0;
+        AlignParams p;
+        ExtendParams e;
+        if (params) {
+            CHECK_ARG(params->reserved[0] == 0 && params->reserved[1] == 0, "align: reserved fields must be 0");
+            if (params->band >= 0) p.band = params->band;
+            if (params->max_cells > 0) p.max_cells = params->max_cells;
+            if (params->ext_band >= 0) e.ext_band = params->ext_band;
+            if (params->match >= 0) e.match = params->match;
+            if (params->mismatch >= 0) e.mismatch = params->mismatch;
+            if (params->gap >= 0) e.gap = params->gap;
+            if (params->xdrop >= 0) e.xdrop = params->xdrop;
+        }
+        AlignResult r;
+        try {
+            index_align_extend(use(ctx->c), idx->d, qs, off, nq, chain_off, strand, member_off, member_q, member_r,
+                               member_len, nchain, nmember, p, e, r);
+        } catch (...) {
+            if (cells_total) *cells_total = r.cells_total;   // the count a tripped cap reports
+            throw;
+        }
+        if (cells_total) *cells_total = r.cells_total;
+        if (gaps) std::copy(r.gaps, r.gaps + 3, gaps);
+        if (ext_rows) *ext_rows = r.ext_rows;
+        *cigar_off = malloc_copy(r.cigar_off);
+        *cigar = malloc_copy(r.cigar);
+        *nm = malloc_copy(r.nm);
+        *n_eq = malloc_copy(r.n_eq);
+        *cols = malloc_copy(r.cols);
+        *aq_start = malloc_copy(r.aq_start);
+        *aq_end = malloc_copy(r.aq_end);
+        *ar_start = malloc_copy(r.ar_start);
+        *ar_end = malloc_copy(r.ar_end);
+        *head_score = malloc_copy(r.head_score);
+        *tail_score = malloc_copy(r.tail_score);
+        *ncigar = (int64_t)r.cigar.size();
+    });
+}
+
 static LibParams lib_params(const bwtmi_lib_params *p) {
     LibParams q;
     if (p) {

@@ -534,11 +534,21 @@ struct AlignResult {
     std::vector<int64_t> ar_start, ar_end;
     int64_t cells_total = 0;
     int64_t gaps[3] = {0, 0, 0};                           // no DP, one lane, one wave
+    std::vector<int32_t> head_score, tail_score;           // per chain; index_align_extend only
+    int64_t ext_rows = 0;                                  // DP rows of all heads and tails; index_align_extend only
+};
+struct ExtendParams {   // resolved; the limits are checked by index_align_extend
+    int32_t ext_band = 32, match = 1, mismatch = 3, gap = 3, xdrop = 30;
 };
 // the arrays of a MapResult (host); validates them before anything reaches the device
 void index_align_chains(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq,
                         const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
                         const int32_t *mq, const int64_t *mr, const int32_t *mlen, int64_t nchain, int64_t nmember,
                         const AlignParams &p, AlignResult &out);
+// the same, and every chain extended past its outer anchors (bwtmi_index_align_extend)
+void index_align_extend(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *off, int64_t nq,
+                        const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
+                        const int32_t *mq, const int64_t *mr, const int32_t *mlen, int64_t nchain, int64_t nmember,
+                        const AlignParams &p, const ExtendParams &e, AlignResult &out);
 
 }  // namespace bwtmi

@@ -568,6 +568,74 @@ int bwtmi_index_align_chains(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs
                              int32_t **aq_end, int64_t **ar_start, int64_t **ar_end, int64_t *ncigar,
                              int64_t *cells_total, int64_t *gaps);
 
+/* ------------------------------------------------------------ extension past the outer anchors
+ * bwtmi_index_align_chains and, per chain, a scored banded DP with X-drop from
+ * each outer anchor towards the read's end (align.hip): the alignment then ends
+ * where the read ends, or where the match ends.  Inputs, S, T, blocks, gaps, the
+ * gap DP and its band W are exactly those of bwtmi_index_align_chains (the
+ * "middle" below is its CIGAR).  With |S| the query's bytes and tn the text's:
+ *   tail     a = S[qe_last, |S|), of m bytes, against b = T[re_last, re_last +
+ *            n), n = min(tn - re_last, m + We).  Cell (i, j), 0 <= i <= m, 0 <= j
+ *            <= n, exists when |j - i| <= We.  H[0][j] = -G j.  For i >= 1, H[i][j]
+ *            is the maximum over the sources that exist of
+ *              H[i-1][j-1] + (a[i-1] == b[j-1] ? A : -B)
+ *              H[i][j-1] - G
+ *              H[i-1][j] - G
+ *            Bytes compare by equality.  No zero floor, no per-cell pruning.
+ *   rows     are computed in order i = 1, 2, ...; a row with no cell ends the
+ *            extension.  The best cell starts as (0, 0) with score 0; a cell
+ *            replaces it only when strictly greater, rows ascending, then j
+ *            ascending: ties keep the smaller i, then the smaller j.  After row
+ *            i, if best - max(row i) > X the extension ends: later rows do not
+ *            exist (X-drop).
+ *   trace    from the best cell to (0, 0); at each cell the first of diagonal
+ *            ('=' or 'X'), left ('D') and up ('I') whose source exists and
+ *            reproduces H[i][j]: the gap DP's preference.
+ *   head     the same rule on the reversed strings: a'[i] = S[q_0 - 1 - i], m =
+ *            q_0; b'[j] = T[r_0 - 1 - j], n = min(r_0, m + We); its operations
+ *            are then reversed.
+ *   empty    m = 0 or n = 0: no extension, score 0, no rows, no cells.
+ *   result   the CIGAR is head, middle, tail, adjacent equal operations merged.
+ *            nm, n_eq, cols and the span aq_* / ar_* include both extensions (the
+ *            best cells' i lengthen the query span, their j the text span); aq_*
+ *            stay in the original query's coordinates on both strands.
+ *            head_score, tail_score (int32 per chain): the two best scores.
+ *            *ext_rows (may be NULL): the rows computed, summed over all heads
+ *            and tails of the call.
+ *   params   band, max_cells: as bwtmi_align_params.  ext_band = We, default 32,
+ *            0..1024; match = A, default 1, 1..64; mismatch = B, default 3, 0..64;
+ *            gap = G, default 3, 1..64; xdrop = X, default 30, 0..2^20.  A negative
+ *            value selects the default.  The defaults are choices (the penalties
+ *            of a short-read aligner with a linear gap; an X that ten mismatches
+ *            in a row exhaust), not measurements.  params = NULL: all defaults.
+ *   cap      the call's count is the gaps' cells plus, per non-empty extension,
+ *            (i* + 1) (2 We + 1) with i* the best cell's row.  The gaps' part is
+ *            checked before anything reaches the device; the whole once the best
+ *            cells are known.  Either way the call fails with BWTMI_E_NOMEM and
+ *            the count in the message and in *cells_total; nothing is
+ *            truncated.  The device's scratch for the extensions' directions is
+ *            one byte per cell counted here, and two rows of 2 We + 2 ints per
+ *            extension in flight.
+ *   out      the nine arrays of bwtmi_index_align_chains, then head_score and
+ *            tail_score: eleven malloc'd arrays (never NULL on success; free with
+ *            bwtmi_free).  gaps as there: extensions are not gaps.
+ *   errors   those of bwtmi_index_align_chains, a new field out of range, a
+ *            nonzero reserved field, and a query with a chain of match * |Q| >=
+ *            2^30 (a score has 31 bits): BWTMI_E_ARG before anything reaches the
+ *            device, every output pointer NULL and every count 0. */
+typedef struct {
+    int32_t band, ext_band, match, mismatch, gap, xdrop, reserved[2];
+    int64_t max_cells;
+} bwtmi_extend_params;
+int bwtmi_index_align_extend(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
+                             const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
+                             const int32_t *member_q, const int64_t *member_r, const int32_t *member_len,
+                             int64_t nchain, int64_t nmember, const bwtmi_extend_params *params, int64_t **cigar_off,
+                             uint32_t **cigar, int32_t **nm, int32_t **n_eq, int32_t **cols, int32_t **aq_start,
+                             int32_t **aq_end, int64_t **ar_start, int64_t **ar_end, int32_t **head_score,
+                             int32_t **tail_score, int64_t *ncigar, int64_t *cells_total, int64_t *gaps,
+                             int64_t *ext_rows);
+
 /* ------------------------------------------------------------ repeat job
  * Replaces the per-contig worker result handling and the post-processing of
  * TandemRepeatFinder (bwt.py:3040-3141, 3402-3944) and save_results with

@@ -13,11 +13,17 @@ HIP-event time from one more pair of calls (align_upload is the chains' way back
 up, timed on the stream like a kernel), the gaps by class, cells_total, and
 digests of both results.
 
-    python tools/align_bench.py OUT.json [--bp N] [--reads N] [--long-reads N] [--long-bp M]
+    python tools/align_bench.py OUT.json [--extend] [--bp N] [--reads N] [--long-reads N] [--long-bp M]
 
-With --untouched: only map_batch on the first two workloads, from the package
-under --tree (default: this tree), so that two trees can be run alternately;
-prints one JSON line with the wall times and the result digests.
+With --extend: every workload also through align_chains(extend=True)
+on the same chains -- its wall time, the new kernels' times, ext_rows, the
+extensions' cells, a digest, and the share of the reads whose first chain's
+alignment spans the whole read, without and with extension.
+
+With --untouched: only map_batch and the plain align_chains on the first two
+workloads, from the package under --tree (default: this tree), so that two
+trees can be run alternately; prints one JSON line with the wall times and the
+result digests.
 
     python tools/align_bench.py --untouched [--tree DIR]
 """
@@ -57,7 +63,40 @@ def _walls(call, reps):
     return walls, got
 
 
-def run(ctx, core, reads, long, reps):
+def extend_digest(got):
+    return _sha((got.cigar_offsets, got.cigar, got.nm, got.n_eq, got.cols, got.qstart, got.qend, got.rstart, got.rend,
+                 got.head_score, got.tail_score))
+
+
+def whole_read_share(reads, res, aln):
+    """the share of the reads whose first chain's alignment spans the whole read"""
+    first, has = res.offsets[:-1], res.offsets[1:] > res.offsets[:-1]
+    qlen = np.array([len(r) for r in reads])
+    k = first[has]
+    return round(float(((aln.qstart[k] == 0) & (aln.qend[k] == qlen[has])).sum()) / max(len(reads), 1), 4)
+
+
+def run_extend(ctx, core, reads, res, aln, reps):
+    """align_chains(extend=True) on the chains `res`, next to the plain result `aln`"""
+    from bwtmi import _lib
+    from smem_bench import _kern
+    walls, ext = _walls(lambda: core.align_chains(reads, res, extend=True), reps)
+    _lib.kernel_stats(ctx, enable=True, reset=True)
+    core.align_chains(reads, res, extend=True)
+    ks = _lib.kernel_stats(ctx, enable=False, reset=True)
+    return dict(ext_band=32, match=1, mismatch=3, gap=3, xdrop=30,
+                extend_wall_ms=min(walls), extend_wall_ms_repeats=walls, ext_rows=int(ext.ext_rows),
+                extension_cells=int(ext.cells_total - aln.cells_total), cells_total=int(ext.cells_total),
+                cigar_operations=int(ext.cigar.size), nm_total=int(ext.nm.sum()), columns_total=int(ext.cols.sum()),
+                heads_extended=int((ext.head_score > 0).sum()), tails_extended=int((ext.tail_score > 0).sum()),
+                whole_read_share_plain=whole_read_share(reads, res, aln),
+                whole_read_share_extended=whole_read_share(reads, res, ext),
+                extend_kernels_ms=round(sum(v[0] for k, v in ks.items() if k.startswith("k_extend")), 4),
+                all_timed_ms=round(sum(v[0] for v in ks.values()), 4), kernels=_kern(ks),
+                extend_sha256=extend_digest(ext))
+
+
+def run(ctx, core, reads, long, reps, extend=False):
     from bwtmi import _lib
     from smem_bench import _kern
     mapper = lambda: core.map_batch(reads, min_len=19, both_strands=True, long=long)   # noqa: E731
@@ -71,6 +110,7 @@ def run(ctx, core, reads, long, reps):
     ks = _lib.kernel_stats(ctx, enable=False, reset=True)
     kern_ms = sum(v[0] for k, v in ks.items() if k.startswith("k_align"))
     ngap = sum(aln.gaps)
+    more = dict(extend=run_extend(ctx, core, reads, res, aln, reps)) if extend else {}
     return dict(reads=len(reads), read_bp=len(reads[0]), long_entry=long, min_len=19, both_strands=True, band=32,
                 map_wall_ms=min(map_walls), map_wall_ms_repeats=map_walls,
                 map_then_align_wall_ms=min(both_walls), map_then_align_wall_ms_repeats=both_walls,
@@ -81,7 +121,7 @@ def run(ctx, core, reads, long, reps):
                 nm_total=int(aln.nm.sum()), columns_total=int(aln.cols.sum()),
                 align_kernels_ms=round(kern_ms, 4), align_upload_ms=round(ks.get("align_upload", (0.0,))[0], 4),
                 align_all_timed_ms=round(sum(v[0] for v in ks.values()), 4), kernels=_kern(ks),
-                map_sha256=map_digest(res), align_sha256=align_digest(aln))
+                map_sha256=map_digest(res), align_sha256=align_digest(aln), **more)
 
 
 def workloads(seq, reads, long_reads, long_bp):
@@ -95,6 +135,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out", nargs="?")
     ap.add_argument("--untouched", action="store_true")
+    ap.add_argument("--extend", action="store_true")
     ap.add_argument("--tree", default=REPO)
     ap.add_argument("--bp", type=int, default=10_000_000)
     ap.add_argument("--reads", type=int, default=10_000)
@@ -112,7 +153,9 @@ def main():
         out = dict(tree=os.path.abspath(a.tree), lib=_lib.source_hash()[:12])
         for name, reads, lng, reps in (("short", short, False, 5), ("long", long, True, 3)):
             walls, res = _walls(lambda: core.map_batch(reads, min_len=19, both_strands=True, long=lng), reps)
-            out[name] = dict(map_wall_ms=min(walls), map_wall_ms_repeats=walls, map_sha256=map_digest(res))
+            awalls, aln = _walls(lambda: core.align_chains(reads, res), reps)
+            out[name] = dict(map_wall_ms=min(walls), map_wall_ms_repeats=walls, map_sha256=map_digest(res),
+                             align_wall_ms=min(awalls), align_wall_ms_repeats=awalls, align_sha256=align_digest(aln))
         core.clear()
         print(json.dumps(out), flush=True)
         return
@@ -120,8 +163,8 @@ def main():
         ap.error("OUT.json is required")
     mid = a.long_bp // 2
     tract = [r[:mid] + r[mid + 75:] for r in long]
-    runs = dict(bp=a.bp, short_reads=run(ctx, core, short, False, 5), long_reads=run(ctx, core, long, True, 3),
-                tract_reads=run(ctx, core, tract, True, 3))
+    runs = dict(bp=a.bp, short_reads=run(ctx, core, short, False, 5, a.extend),
+                long_reads=run(ctx, core, long, True, 3, a.extend), tract_reads=run(ctx, core, tract, True, 3, a.extend))
     core.clear()
     print(json.dumps(runs), flush=True)
     with open(a.out, "w") as fh:
