@@ -8,9 +8,11 @@ from .motif import MotifUtils, RepeatAlignmentSummary
 from .core import BWTCore
 from .tiers import Tier1STRFinder, Tier2LCPFinder, Tier3LongReadFinder
 from .finder import TandemRepeatFinder
+from .select import merge_groups, select_chains
 
 __all__ = ["TandemRepeat", "Job", "RepeatList", "MotifUtils", "RepeatAlignmentSummary", "BWTCore",
-           "Tier1STRFinder", "Tier2LCPFinder", "Tier3LongReadFinder", "TandemRepeatFinder", "main"]
+           "Tier1STRFinder", "Tier2LCPFinder", "Tier3LongReadFinder", "TandemRepeatFinder", "merge_groups",
+           "select_chains", "main"]
 
 
 def main(argv=None):

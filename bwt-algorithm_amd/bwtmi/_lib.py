@@ -47,6 +47,11 @@ class ExtendParams(C.Structure):
                 ("gap", C.c_int32), ("xdrop", C.c_int32), ("reserved", C.c_int32 * 2), ("max_cells", C.c_int64)]
 
 
+class SelectParams(C.Structure):
+    _fields_ = [("mask", C.c_int32), ("pri_ratio", C.c_int32), ("best_n", C.c_int32), ("full", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
 class LibParams(C.Structure):
     _fields_ = [("min_period", C.c_int32), ("max_period", C.c_int32), ("max_short_motif", C.c_int32),
                 ("min_copies", C.c_int32), ("min_array_length", C.c_int32), ("allow_mismatches", C.c_int32),
@@ -102,6 +107,8 @@ _SIGS = {
     "bwtmi_index_map_batch": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_uint32, C.c_int64, C.c_int64,
                                         C.POINTER(ChainParams)] + [C.POINTER(C.c_void_p)] * 12 +
                               [C.POINTER(C.c_int64)] * 6),
+    "bwtmi_select_chains": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.POINTER(SelectParams)] +
+                            [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_int64)] * 2),
     "bwtmi_index_align_chains": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64,
                                            C.POINTER(AlignParams)] + [C.POINTER(C.c_void_p)] * 9 +
                                  [C.POINTER(C.c_int64)] * 2 + [_P]),
@@ -417,6 +424,52 @@ def chain_anchors(h, group_off, q, r, length, **params) -> dict:
         counts = (ng + 1, n, n, n, n, n, n, n + 1, nm.value)
         out = {k: take(p, t, c) for k, p, t, c in zip(names, ptrs, kinds, counts)}
         out["evals"] = ev.value
+        return out
+    finally:
+        for p in ptrs:
+            lib().bwtmi_free(p)
+
+
+SELECT_PARAMS = ("mask", "pri_ratio", "best_n", "full")
+
+
+def select_chains(h, chain_off, score, qstart, qend, mask=None, pri_ratio=None, best_n=None, full=None,
+                  reserved=None) -> dict:
+    """The device selection (bwtmi_select_chains) on chain rows (score, qstart,
+    qend) in groups chain_off[ng + 1], one group per read: a dict of parent
+    (int32, relative to the group's first chain), sub (int32), mapq, keep
+    (uint8), n_primary and n_kept.  A parameter left None takes the library's
+    default.  ValueError on BWTMI_E_ARG."""
+    import numpy as np
+    co = np.ascontiguousarray(chain_off, dtype=np.int64)
+    sc, qs, qe = (np.ascontiguousarray(a, dtype=np.int32) for a in (score, qstart, qend))
+    if co.ndim != 1 or co.size < 1 or not sc.size == qs.size == qe.size:
+        raise ValueError("chain_off needs ng + 1 entries, score / qstart / qend equal sizes")
+    if co[-1] != sc.size:
+        raise ValueError(f"chain_off ends at {int(co[-1])}, the chain arrays hold {sc.size}")
+    sp = SelectParams()
+    for k, v in zip(SELECT_PARAMS, (mask, pri_ratio, best_n, full)):
+        if v is not None and int(v) < 0:
+            raise ValueError(f"{k} must not be negative")
+        setattr(sp, k, -1 if v is None else int(v))
+    for i, v in enumerate(reserved or ()):
+        sp.reserved[i] = int(v)
+    ptrs = [C.c_void_p() for _ in range(4)]
+    npri, nkept = C.c_int64(0), C.c_int64(0)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None      # noqa: E731
+    rc = lib().bwtmi_select_chains(h, co.ctypes.data_as(C.c_void_p), co.size - 1, ptr(sc), ptr(qs), ptr(qe), C.byref(sp),
+                                   *[C.byref(p) for p in ptrs], C.byref(npri), C.byref(nkept))
+    if rc == -1:   # BWTMI_E_ARG: every output pointer is NULL, every count 0
+        clean = all(p.value is None for p in ptrs) and npri.value == 0 and nkept.value == 0
+        msg = lib().bwtmi_last_error()
+        raise ValueError((msg.decode(errors="replace") if msg else "bad argument") +
+                         ("" if clean else " [outputs were written]"))
+    check(rc)
+    try:
+        n = sc.size
+        out = {k: take(p, t, n) for k, p, t in zip(("parent", "sub", "mapq", "keep"), ptrs,
+                                                   (np.int32, np.int32, np.uint8, np.uint8))}
+        out["n_primary"], out["n_kept"] = npri.value, nkept.value
         return out
     finally:
         for p in ptrs:

@@ -137,6 +137,28 @@ class MapResult:
         return np.stack([self.member_q[a:b].astype(np.int64), self.member_r[a:b],
                          self.member_len[a:b].astype(np.int64)], axis=1)
 
+    def take(self, keep) -> "MapResult":
+        """The chains with keep != 0 (one flag per chain), in their order, as a
+        MapResult of the same queries: exactly the arrays map_batch returns, so
+        align_chains and map_rows take it unchanged.  Offsets and members are
+        rebuilt; the four counters are carried over."""
+        keep = np.asarray(keep).astype(bool).reshape(-1)
+        if keep.size != self.strand.size:
+            raise ValueError(f"keep has {keep.size} flags for {self.strand.size} chains")
+        offsets = np.asarray(self.offsets, dtype=np.int64)
+        moff = np.asarray(self.member_offsets, dtype=np.int64)
+        before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])      # kept chains ahead of chain k
+        sizes = (moff[1:] - moff[:-1])[keep]
+        new_moff = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)])
+        # member t of the result is member moff[k] + (t - new_moff[k']) of its chain k (k' its new index)
+        owner = np.repeat(np.arange(sizes.size, dtype=np.int64), sizes)
+        src = moff[:-1][keep][owner] + (np.arange(owner.size, dtype=np.int64) - new_moff[:-1][owner])
+        cols = [np.asarray(getattr(self, k))[keep] for k in ("strand", "score", "n_anchors", "qstart", "qend", "rstart",
+                                                             "rend")]
+        mem = [np.asarray(getattr(self, k))[src] for k in ("member_q", "member_r", "member_len")]
+        return MapResult(before[offsets], *cols, new_moff, *mem, self.positions_total, self.skipped_smems, self.anchors,
+                         self.evals)
+
     def __getitem__(self, i: int):
         if not -len(self) <= i < len(self):
             raise IndexError(i)

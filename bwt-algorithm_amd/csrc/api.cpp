@@ -886,6 +886,59 @@ int bwtmi_index_map_batch(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, c
     });
 }
 
+// ------------------------------------------------------------ selection
+int bwtmi_select_chains(bwtmi_ctx *ctx, const int64_t *chain_off, int64_t ng, const int32_t *score,
+                        const int32_t *qstart, const int32_t *qend, const bwtmi_select_params *params,
+                        int32_t **parent, int32_t **sub, uint8_t **mapq, uint8_t **keep, int64_t *n_primary,
+                        int64_t *n_kept) {
+    return guard([&] {
+        CHECK_ARG(ctx && parent && sub && mapq && keep, "bad argument");
+        *parent = *sub = nullptr;
+        *mapq = *keep = nullptr;
+        if (n_primary) *n_primary = 0;
+        if (n_kept) *n_kept = 0;
+        SelectParams p;
+        if (params) {
+            for (int32_t v : params->reserved) CHECK_ARG(v == 0, "select: reserved fields must be 0");
+            if (params->mask >= 0) p.mask = params->mask;
+            if (params->pri_ratio >= 0) p.pri_ratio = params->pri_ratio;
+            if (params->best_n >= 0) p.best_n = params->best_n;
+            if (params->full >= 0) p.full = params->full;
+        }
+        if (p.mask < 1 || p.mask > 100) fail(BWTMI_E_ARG, "select: mask %d outside 1..100", (int)p.mask);
+        if (p.pri_ratio > 100) fail(BWTMI_E_ARG, "select: pri_ratio %d outside 0..100", (int)p.pri_ratio);
+        if (p.full < 1 || p.full > (1 << 20)) fail(BWTMI_E_ARG, "select: full %d outside 1..2^20", (int)p.full);
+        CHECK_ARG(ng >= 0, "select: ng must not be negative");
+        CHECK_ARG(chain_off, "select: null chain_off");
+        CHECK_ARG(chain_off[0] == 0, "select: chain_off[0] must be 0");
+        for (int64_t g = 0; g < ng; ++g)
+            if (chain_off[g + 1] < chain_off[g])
+                fail(BWTMI_E_ARG, "select: chain_off decreases at group %lld", (long long)g);
+        const int64_t nc = chain_off[ng];
+        CHECK_ARG(nc == 0 || score, "select: null score array");
+        CHECK_ARG(nc == 0 || qstart, "select: null qstart array");
+        CHECK_ARG(nc == 0 || qend, "select: null qend array");
+        int32_t max_score = 0;
+        for (int64_t i = 0; i < nc; ++i) {
+            if (score[i] < 1 || score[i] > (1 << 30))
+                fail(BWTMI_E_ARG, "select: score %d of chain %lld outside 1..2^30", (int)score[i], (long long)i);
+            if (qstart[i] < 0) fail(BWTMI_E_ARG, "select: qstart %d of chain %lld is negative", (int)qstart[i], (long long)i);
+            if (qend[i] <= qstart[i] || qend[i] > (1 << 28))
+                fail(BWTMI_E_ARG, "select: qend %d of chain %lld outside qstart %d < qend <= 2^28", (int)qend[i],
+                     (long long)i, (int)qstart[i]);
+            max_score = std::max(max_score, score[i]);
+        }
+        SelectResult r;
+        select_chains_device(use(ctx->c), chain_off, ng, score, qstart, qend, max_score, p, r);
+        *parent = malloc_copy(r.parent);
+        *sub = malloc_copy(r.sub);
+        *mapq = malloc_copy(r.mapq);
+        *keep = malloc_copy(r.keep);
+        if (n_primary) *n_primary = r.n_primary;
+        if (n_kept) *n_kept = r.n_kept;
+    });
+}
+
 int bwtmi_index_align_chains(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs, const int64_t *off, int64_t nq,
                              const int64_t *chain_off, const uint8_t *strand, const int64_t *member_off,
                              const int32_t *member_q, const int64_t *member_r, const int32_t *member_len,

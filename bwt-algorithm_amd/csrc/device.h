@@ -522,6 +522,20 @@ void index_map_batch(Ctx &c, DeviceIndex *ix, const uint8_t *qs, const int64_t *
                      bool both_strands, bool long_entry, int64_t max_occ, int64_t max_positions, const ChainParams &p,
                      MapResult &out);
 
+// ----- primary / secondary, MAPQ and pruning of a read's chains (select.hip; contract in bwtmi.h)
+struct SelectParams {   // resolved, as ChainParams is
+    int32_t mask = 50, pri_ratio = 80, best_n = 5, full = 100;
+};
+struct SelectResult {
+    std::vector<int32_t> parent, sub;   // per chain, in input order
+    std::vector<uint8_t> mapq, keep;
+    int64_t n_primary = 0, n_kept = 0;
+};
+// group g = chains [chain_off[g], chain_off[g + 1]) of score / qstart / qend (host
+// arrays, validated by the caller; max_score = the largest score, 0 without chains)
+void select_chains_device(Ctx &c, const int64_t *chain_off, int64_t ng, const int32_t *score, const int32_t *qstart,
+                          const int32_t *qend, int32_t max_score, const SelectParams &p, SelectResult &out);
+
 // ----- base-level alignment of chains (align.hip; contract in bwtmi.h)
 struct AlignParams {   // resolved, as ChainParams is
     int32_t band = 32;

@@ -3,7 +3,9 @@
 chained on the device, one PAF row per chain:
 
     python map.py IN.fa QUERIES [-l MIN_LEN] [--both-strands] [--long] [--max-occ N] [--max-gap N]
-                  [--bandwidth N] [--min-score N] [--min-anchors N] -o OUT.paf
+                  [--bandwidth N] [--min-score N] [--min-anchors N] [--cigar] [--extend] [--select] -o OUT.paf
+
+(bwtmi/map.py lists every option.)
 """
 import os
 import sys

@@ -636,6 +636,59 @@ int bwtmi_index_align_extend(bwtmi_ctx *ctx, bwtmi_index *idx, const uint8_t *qs
                              int32_t **tail_score, int64_t *ncigar, int64_t *cells_total, int64_t *gaps,
                              int64_t *ext_rows);
 
+/* ------------------------------------------------------------ selection of a read's chains
+ * Which of a read's chains is its placement, which are echoes of it, and how far
+ * the placement is to be trusted (not in the reference): primary / secondary,
+ * MAPQ and the pruning of weak secondaries, on the device (select.hip), before
+ * any alignment.  The entry works on chain rows only and takes no index, so a
+ * group may hold one read's chains from both strands and from several contigs'
+ * indexes.  Everything is in integers, with products in 64 bits.
+ *   in       chain_off[ng + 1] (chain_off[0] = 0): group g = chains [chain_off[g],
+ *            chain_off[g + 1]); score, qstart, qend (int32), one per chain.  A
+ *            group is one read.  qstart / qend are the original query's
+ *            coordinates, as bwtmi_index_map_batch returns them, so intervals of
+ *            both strands compare directly.
+ *   rank     inside a group: by (score descending, input index ascending).
+ *   parent   visit the group's chains in rank order, keeping the list P of
+ *            primaries in the order found.  For chain c take the first p in P with
+ *              ov(c, p) * 100 >= mask * min(qend_c - qstart_c, qend_p - qstart_p)
+ *              ov = max(0, min(qend_c, qend_p) - max(qstart_c, qstart_p)).
+ *            If there is one, c is secondary and parent[c] = p; if sub[p] is
+ *            still 0, sub[p] = score_c (the best secondary, by the rank order).
+ *            Otherwise c is primary: parent[c] = c, sub[c] = 0, and c is appended
+ *            to P.  Overlap is judged per primary, never summed over primaries.
+ *   keep     primaries: always.  Secondaries in rank order: c is kept when
+ *              score_c * 100 >= pri_ratio * score_parent(c)
+ *            and fewer than best_n secondaries of this group have been kept so far.
+ *   mapq     primary: floor(60 * (s1 - sub) * min(s1, full) / (s1 * full)) with s1
+ *            its score, in 0..60; secondary: 0.
+ *   out      parent (int32: the parent's index relative to its group's first
+ *            chain, in input order; a primary's own), sub (int32; 0 for a
+ *            secondary and for a primary without one), mapq (uint8), keep (uint8
+ *            0 / 1), one per chain in input order.  All four are malloc'd (never
+ *            NULL on success, no chains included; free with bwtmi_free).
+ *            *n_primary, *n_kept (each may be NULL): the primaries, and the kept
+ *            chains, primaries included.
+ *   params   a negative value selects the default: mask 50 (legal 1..100),
+ *            pri_ratio 80 (0..100), best_n 5 (>= 0; 0 = primaries only), full 100
+ *            (1..2^20).  The defaults are choices (the usual read-mapper values
+ *            for the first three; a score at which a unique chain earns the full
+ *            60), not measurements.  params = NULL: all defaults.
+ *   errors   BWTMI_E_ARG before anything reaches the device, every output pointer
+ *            NULL and every count 0: ng < 0; offsets that decrease or do not
+ *            start at 0; qstart < 0, qend <= qstart or qend > 2^28; score < 1 or
+ *            score > 2^30; mask 0 or > 100; pri_ratio > 100; full 0 or > 2^20; a
+ *            nonzero reserved field; a null array with chains present.
+ *            BWTMI_E_NOMEM: 2^31 chains or groups and more.  ng = 0 and empty
+ *            groups are legal.  There is no cap on a group's size. */
+typedef struct {
+    int32_t mask, pri_ratio, best_n, full, reserved[4];
+} bwtmi_select_params;
+int bwtmi_select_chains(bwtmi_ctx *ctx, const int64_t *chain_off, int64_t ng, const int32_t *score,
+                        const int32_t *qstart, const int32_t *qend, const bwtmi_select_params *params,
+                        int32_t **parent, int32_t **sub, uint8_t **mapq, uint8_t **keep, int64_t *n_primary,
+                        int64_t *n_kept);
+
 /* ------------------------------------------------------------ repeat job
  * Replaces the per-contig worker result handling and the post-processing of
  * TandemRepeatFinder (bwt.py:3040-3141, 3402-3944) and save_results with
